@@ -6,7 +6,11 @@ inputs already resident in HBM (the snapshot is encoded and uploaded once, like 
 Solve does not shard (every placement depends on all earlier ones), so N GPUs run N independent
 replicas, one per rank ("replicas only"); value = pods solved by all ranks / max-rank time.
 
-Prints ONE JSON line on rank 0 (the driver's contract), including:
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline figure needs: it encodes and
+uploads the problem, runs one untimed Solve (which settles the launch plan) and the W warm-up Solves, times
+the N steps and prints ONE JSON line on rank 0 (the driver's contract) with metric, value, unit,
+higher_is_better, dtype and ms_per_step.  `--dump-outputs DIR` also writes the Results of that Solve as
+DIR/<name>.npy (_dump_outputs).  `--full` adds everything else to the line:
   create_ms / e2e_*  what a drop-in caller pays: ks_problem_create (parse + encode + upload, the
                      NewScheduler-time work) and the rate including it and the results copy-back
   roofline     : dominant kernel k_solve, HIP-event duration vs the 8 TB/s HBM peak, for two byte
@@ -176,6 +180,56 @@ def _create_binary(h, cls):
     load_ms = (time.perf_counter() - t) * 1000.0
     x.close()
     return save_ms, load_ms, len(blob)
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def _dump_outputs(path, sch, local, npods, alg_bytes):
+    """--dump-outputs: the Results of the timed Solve as float64 arrays, path/<name>.npy.
+
+    The timed steps leave their Results in HBM (timing_only: no copy-back), so they are read from one more Solve
+    of the same handle after the timed steps, with the copy-back, through the structured accessors; a Solve
+    starts from fresh scheduler state and is deterministic, so it computes what the last timed step computed.
+    algorithmic_bytes is the last timed step's own counter.  One element per input pod, so their shapes
+    depend on the problem alone: pod_nodeclaim (index of the pod's NewNodeClaim in Results order, -1: none),
+    pod_existing_node (state node index, -1: none), pod_position (the pod's place in its NodeClaim's or node's
+    pod list, -1: neither), pod_error (1: in PodErrors).  One element per NewNodeClaim: nodeclaim_template,
+    nodeclaim_pod_counts, nodeclaim_instance_type_counts, and nodeclaim_instance_types (every claim's instance
+    type indices, concatenated in Results order); a Solve that makes no NodeClaim writes none of these four,
+    never an empty array.  Should the arrays exceed 64 MB in all, every array over its share is cut to a fixed,
+    seeded sample of its elements.  Returns the NewNodeClaims count."""
+    import numpy as np
+
+    r = sch.solve_structured(device=local)
+    pod_claim, pod_node, pod_pos, pod_err = (np.full(npods, v, np.float64) for v in (-1.0, -1.0, -1.0, 0.0))
+    for i, c in enumerate(r.new_nodeclaims):
+        pod_claim[c["pods"]] = i
+        pod_pos[c["pods"]] = np.arange(len(c["pods"]))
+    for n, pods in r.existing_nodes:
+        pod_node[pods] = n
+        pod_pos[pods] = np.arange(len(pods))
+    pod_err[sorted(r.pod_errors)] = 1.0
+    arrays = {"pod_nodeclaim": pod_claim, "pod_existing_node": pod_node, "pod_position": pod_pos, "pod_error": pod_err,
+              "algorithmic_bytes": np.array([alg_bytes], np.float64)}
+    if r.new_nodeclaims:
+        arrays.update({
+            "nodeclaim_template": np.array([c["template"] for c in r.new_nodeclaims], np.float64),
+            "nodeclaim_pod_counts": np.array([len(c["pods"]) for c in r.new_nodeclaims], np.float64),
+            "nodeclaim_instance_type_counts": np.array([len(c["instance_types"]) for c in r.new_nodeclaims], np.float64),
+            "nodeclaim_instance_types": np.concatenate([np.asarray(c["instance_types"], np.float64)
+                                                        for c in r.new_nodeclaims]),
+        })
+    if sum(a.nbytes for a in arrays.values()) > DUMP_CAP_BYTES:
+        share = DUMP_CAP_BYTES // (8 * len(arrays))  # elements
+        rng = np.random.default_rng(0)
+        for k, a in arrays.items():
+            if a.size > share:
+                arrays[k] = a[np.sort(rng.choice(a.size, share, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return len(r.new_nodeclaims)
 
 
 def consolidation_bench(args, rank, world, local, dist, barrier_sync, topology=0):
@@ -376,6 +430,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline figure: create / "
+                    "structured / collected cost, rooflines, CPU baselines, the C1/C3/C4 Solve lines, consolidation")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the Results of the timed Solve as DIR/<name>.npy")
     ap.add_argument("--pods", type=int, default=50000)
     ap.add_argument("--its", type=int, default=400)
     ap.add_argument("--cpu-pods", type=int, default=50000, help="oracle sample size (same workload shape)")
@@ -399,6 +457,8 @@ def main():
     ap.add_argument("--cons-topo-apps", type=int, default=20, help="topology consolidation line: apps (0: skip)")
     ap.add_argument("--cpu-topo-sims", type=int, default=100, help="oracle sample for the topology consolidation line")
     args = ap.parse_args()
+    if (args.only_consolidation or args.only_solve) and not args.full:
+        ap.error("--only-consolidation and --only-solve select workloads of the full benchmark: add --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -444,16 +504,22 @@ def main():
 
     snap = synth.config2(args.pods) if args.its == 400 else synth.benchmark_snapshot(args.pods, args.its, 42, False)
     snap_json = json.dumps(snap)
-    sch, create_ms = _create(Scheduler, snap_json)
-    save_ms, create_bin_ms, snap_bytes = _create_binary(sch, Scheduler)
+    nclaims = None
+    if args.full:
+        sch, create_ms = _create(Scheduler, snap_json)
+        save_ms, create_bin_ms, snap_bytes = _create_binary(sch, Scheduler)
 
-    # one full solve (results copied back and rendered) to verify the result shape outside the timed region
-    t = time.perf_counter()
-    check = sch.solve(device=local)
-    full_ms = (time.perf_counter() - t) * 1000.0
-    placed = sum(len(c["pods"]) for c in check.new_nodeclaims)
-    assert placed + len(check.pod_errors) == args.pods, "solve lost pods"
-    nclaims = len(check.new_nodeclaims)
+        # one full solve (results copied back and rendered) to verify the result shape outside the timed region
+        t = time.perf_counter()
+        check = sch.solve(device=local)
+        full_ms = (time.perf_counter() - t) * 1000.0
+        placed = sum(len(c["pods"]) for c in check.new_nodeclaims)
+        assert placed + len(check.pod_errors) == args.pods, "solve lost pods"
+        nclaims = len(check.new_nodeclaims)
+    else:
+        sch = Scheduler(snap_json)
+        # the handle's first Solve, outside the timed region as above: it settles the launch plan later Solves reuse
+        sch.solve(device=local, timing_only=True)
 
     for _ in range(args.warmup):
         sch.solve(device=local, timing_only=True)
@@ -467,18 +533,21 @@ def main():
         algb.append(r.algorithmic_bytes)
     barrier_sync()
     elapsed = time.perf_counter() - t0
-    # the same Solves with the Results copied back and read through the structured accessors (what the
-    # drop-in caller does: ks_solve + ks_results_* in INTEGRATION.md's cgo shim, no JSON)
-    barrier_sync()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        sch.solve_structured(device=local)
-    barrier_sync()
-    structured_ms = (time.perf_counter() - t1) * 1000.0 / args.steps
-    # the C-ABI part of that return path alone: ks_solve with the Results collected (the copy-back, the
-    # replayed checks and the claim/node/error tables the accessors hand out) and ks_results_free -- what a cgo
-    # caller pays before its own (C-speed) accessor walk; the Python walk above adds ctypes per field
-    collected_ms = sch.timed_collect(args.steps, device=local)
+    if args.dump_outputs and rank == 0:
+        nclaims = _dump_outputs(args.dump_outputs, sch, local, args.pods, algb[-1])
+    if args.full:
+        # the same Solves with the Results copied back and read through the structured accessors (what the
+        # drop-in caller does: ks_solve + ks_results_* in INTEGRATION.md's cgo shim, no JSON)
+        barrier_sync()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            sch.solve_structured(device=local)
+        barrier_sync()
+        structured_ms = (time.perf_counter() - t1) * 1000.0 / args.steps
+        # the C-ABI part of that return path alone: ks_solve with the Results collected (the copy-back, the
+        # replayed checks and the claim/node/error tables the accessors hand out) and ks_results_free -- what a cgo
+        # caller pays before its own (C-speed) accessor walk; the Python walk above adds ctypes per field
+        collected_ms = sch.timed_collect(args.steps, device=local)
     if dist is not None:
         import torch
 
@@ -487,47 +556,48 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed * 1000.0 / args.steps
     value = args.pods * world * args.steps / elapsed
-    k_ms = sum(solve_ms) / len(solve_ms)
-    bytes_per_launch = sum(algb) / len(algb)
-    ref = _ref_bytes("C2", snap_json)
-    cpu = None
-    if not args.no_cpu_baseline and world == 1:
-        from oracle import bridge
+    if args.full:
+        k_ms = sum(solve_ms) / len(solve_ms)
+        bytes_per_launch = sum(algb) / len(algb)
+        ref = _ref_bytes("C2", snap_json)
+        cpu = None
+        if not args.no_cpu_baseline and world == 1:
+            from oracle import bridge
 
-        csnap = json.dumps(synth.config2(args.cpu_pods)) if args.cpu_pods != args.pods else snap_json
-        res, secs = bridge.solve(csnap)
-        if ref is None and args.cpu_pods == args.pods:
-            ref = res.get("stats", {}).get("algBytesRef")
-        cpu = _baseline(args.cpu_pods / secs, "pods/s", 1, "1 Solve of C2 with %d pods x %d instance types" %
-                        (args.cpu_pods, args.its), secs)
-    lines = {}
-    if world == 1:
-        if not args.no_c1:
-            c1 = synth.config1(literal=True)
-            lines["solve_c1"] = solve_line(
-                args, local, "C1", c1, "pods/sec in Scheduler.Solve (C1: BenchmarkScheduling2000, the benchmark's "
-                "literal pods: empty UIDs, zero timestamps; 400 fake instance types, empty topology)", 200,
-                cpu_sample=(c1, 2000, "20 Solves of C1", 20), traffic_tag="c1")
-        if not args.no_c3:
-            sp = min(args.c3_cpu_pods, args.c3_pods)
-            lines["solve_c3"] = solve_line(
-                args, local, "C3", synth.config3(args.c3_pods),
-                "pods/sec in Scheduler.Solve (C3: %d pods, 800 instance types x 8 offerings, 3 tainted NodePools, "
-                "selectors/affinity/tolerations)" % args.c3_pods, 2,
-                cpu_sample=(synth.config3(sp), sp, "1 Solve of C3 with %d pods (the oracle's per-pod cost grows with "
-                            "the pod count: at 20k it takes ~460 s)" % sp, 1), traffic_tag="c3")
-        if not args.no_c4:
-            sp, sn = max(args.c4_pods // 4, 1), max(args.c4_nodes // 4, 1)
-            lines["solve_c4"] = solve_line(
-                args, local, "C4", synth.config4(args.c4_pods, args.c4_nodes),
-                "pods/sec in Scheduler.Solve (C4: %d pods onto %d existing nodes, zonal + hostname spread, hostname "
-                "anti-affinity, 20 apps)" % (args.c4_pods, args.c4_nodes), 3,
-                cpu_sample=(synth.config4(sp, sn), sp, "1 Solve of C4 with %d pods onto %d nodes" % (sp, sn), 1),
-                traffic_tag="c4")
-    cons = None if args.no_consolidation else consolidation_bench(args, rank, world, local, dist, barrier_sync)
-    ctopo = None
-    if not args.no_consolidation and args.cons_topo_apps:
-        ctopo = consolidation_bench(args, rank, world, local, dist, barrier_sync, args.cons_topo_apps)
+            csnap = json.dumps(synth.config2(args.cpu_pods)) if args.cpu_pods != args.pods else snap_json
+            res, secs = bridge.solve(csnap)
+            if ref is None and args.cpu_pods == args.pods:
+                ref = res.get("stats", {}).get("algBytesRef")
+            cpu = _baseline(args.cpu_pods / secs, "pods/s", 1, "1 Solve of C2 with %d pods x %d instance types" %
+                            (args.cpu_pods, args.its), secs)
+        lines = {}
+        if world == 1:
+            if not args.no_c1:
+                c1 = synth.config1(literal=True)
+                lines["solve_c1"] = solve_line(
+                    args, local, "C1", c1, "pods/sec in Scheduler.Solve (C1: BenchmarkScheduling2000, the benchmark's "
+                    "literal pods: empty UIDs, zero timestamps; 400 fake instance types, empty topology)", 200,
+                    cpu_sample=(c1, 2000, "20 Solves of C1", 20), traffic_tag="c1")
+            if not args.no_c3:
+                sp = min(args.c3_cpu_pods, args.c3_pods)
+                lines["solve_c3"] = solve_line(
+                    args, local, "C3", synth.config3(args.c3_pods),
+                    "pods/sec in Scheduler.Solve (C3: %d pods, 800 instance types x 8 offerings, 3 tainted NodePools, "
+                    "selectors/affinity/tolerations)" % args.c3_pods, 2,
+                    cpu_sample=(synth.config3(sp), sp, "1 Solve of C3 with %d pods (the oracle's per-pod cost grows "
+                                "with the pod count: at 20k it takes ~460 s)" % sp, 1), traffic_tag="c3")
+            if not args.no_c4:
+                sp, sn = max(args.c4_pods // 4, 1), max(args.c4_nodes // 4, 1)
+                lines["solve_c4"] = solve_line(
+                    args, local, "C4", synth.config4(args.c4_pods, args.c4_nodes),
+                    "pods/sec in Scheduler.Solve (C4: %d pods onto %d existing nodes, zonal + hostname spread, "
+                    "hostname anti-affinity, 20 apps)" % (args.c4_pods, args.c4_nodes), 3,
+                    cpu_sample=(synth.config4(sp, sn), sp, "1 Solve of C4 with %d pods onto %d nodes" % (sp, sn), 1),
+                    traffic_tag="c4")
+        cons = None if args.no_consolidation else consolidation_bench(args, rank, world, local, dist, barrier_sync)
+        ctopo = None
+        if not args.no_consolidation and args.cons_topo_apps:
+            ctopo = consolidation_bench(args, rank, world, local, dist, barrier_sync, args.cons_topo_apps)
     if rank != 0:
         dist.destroy_process_group()
         return
@@ -547,28 +617,32 @@ def main():
         "config": {"workload": "C2: %d resource-only pods x %d fake.InstanceTypes, 1 NodeClaimTemplate, no limits, "
                                "empty topology (BenchmarkScheduling shape)" % (args.pods, args.its),
                    "pods": args.pods, "instance_types": args.its, "parallelism": "replicas%d" % world,
+                   # (counted by --full's result check or --dump-outputs; null in a plain run without either)
                    "new_nodeclaims": nclaims},
-        # the drop-in caller's cost (never `value`): ks_problem_create = parse + encode + upload of the
-        # snapshot; e2e = create + one Solve with its results copied back and rendered
-        "create_ms": round(create_ms, 3),
-        "create_binary_ms": round(create_bin_ms, 3),  # Scheduler.from_binary(save()): upload only
-        "full_solve_ms": round(full_ms, 3),
-        # a Solve with its Results read through the structured accessors, per step, and that rate
-        "structured_solve_ms": round(structured_ms, 3),
-        "structured_pods_per_s": round(args.pods * world / (structured_ms / 1000.0), 1),
-        "collected_solve_ms": round(collected_ms, 3),
-        "collected_over_kernel_only": round(collected_ms / (elapsed * 1000.0 / args.steps), 3) if elapsed else None,
-        "e2e_pods_per_s": round(args.pods / ((create_ms + full_ms) / 1000.0), 1),
-        "roofline": _roofline("k_solve", k_ms, bytes_per_launch, ref, "c2", extra={
-            "setup_kernels_ms": round(sum(total_ms) / len(total_ms) - k_ms, 3),
-            # SURVEY §8d timing protocol: median and p90 (nearest rank) of the timed Solves
-            "kernel_ms_p50": round(_pct(solve_ms, 50), 3), "kernel_ms_p90": round(_pct(solve_ms, 90), 3)}),
-        "cpu_baseline": cpu,
-        "oracle_full_size": _oracle_full("C2", snap_json, args.pods, "pods/s"),
     }
-    out.update(lines)
-    out["consolidation"] = cons
-    out["consolidation_topology"] = ctopo
+    if args.full:
+        out.update({
+            # the drop-in caller's cost (never `value`): ks_problem_create = parse + encode + upload of the
+            # snapshot; e2e = create + one Solve with its results copied back and rendered
+            "create_ms": round(create_ms, 3),
+            "create_binary_ms": round(create_bin_ms, 3),  # Scheduler.from_binary(save()): upload only
+            "full_solve_ms": round(full_ms, 3),
+            # a Solve with its Results read through the structured accessors, per step, and that rate
+            "structured_solve_ms": round(structured_ms, 3),
+            "structured_pods_per_s": round(args.pods * world / (structured_ms / 1000.0), 1),
+            "collected_solve_ms": round(collected_ms, 3),
+            "collected_over_kernel_only": round(collected_ms / (elapsed * 1000.0 / args.steps), 3) if elapsed else None,
+            "e2e_pods_per_s": round(args.pods / ((create_ms + full_ms) / 1000.0), 1),
+            "roofline": _roofline("k_solve", k_ms, bytes_per_launch, ref, "c2", extra={
+                "setup_kernels_ms": round(sum(total_ms) / len(total_ms) - k_ms, 3),
+                # SURVEY §8d timing protocol: median and p90 (nearest rank) of the timed Solves
+                "kernel_ms_p50": round(_pct(solve_ms, 50), 3), "kernel_ms_p90": round(_pct(solve_ms, 90), 3)}),
+            "cpu_baseline": cpu,
+            "oracle_full_size": _oracle_full("C2", snap_json, args.pods, "pods/s"),
+        })
+        out.update(lines)
+        out["consolidation"] = cons
+        out["consolidation_topology"] = ctopo
     print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -1,4 +1,4 @@
-"""One consolidation pass sharded over the ranks of a torch.distributed group (bench.py --gpus N, and the
+"""One consolidation pass sharded over the ranks of a torch.distributed group (bench.py --full --gpus N, and the
 multi-process GPU tests call exactly this).
 
 Every simulation reads the same immutable cluster problem, so rank r runs the simulations s with

@@ -5,9 +5,9 @@ set -o pipefail
 tag=${1:-r01}
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --cons-steps 3"
-S="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --cons-steps 3 --cons-topo-apps 0"
-C="python3 $R/bench.py --only-consolidation --warmup 1 --no-cpu-baseline --cons-steps 3"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --cons-steps 3"
+S="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --cons-steps 3 --cons-topo-apps 0"
+C="python3 $R/bench.py --full --only-consolidation --warmup 1 --no-cpu-baseline --cons-steps 3"
 out=$R/gpurun_out
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_trace -o run -- $B > $out/prof_${tag}_trace.log 2>&1 || exit $?
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/prof_${tag}_fetch -o run -- $S > $out/prof_${tag}_fetch.log 2>&1 || exit $?

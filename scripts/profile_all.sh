@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 evidence for every bench workload on the build being benched:
-#   trace : kernel trace + stats of the default bench command (minus the CPU baseline legs), so the kernel
+#   trace : kernel trace + stats of the full bench command (bench.py --full, minus the CPU baseline legs), so the kernel
 #           averages are those of the timed launches;
 #   then per workload (C1, C2, C3, C4, C5, C5T, one bench process each): PMC passes FETCH_SIZE, WRITE_SIZE
 #   (HBM bytes, corrected per MI355X_MICROARCH.md in scripts/pmc_summary.py), and two SQ passes (wave cycles,
@@ -13,7 +13,7 @@ W=${@:-c1 c2 c3 c4 c5 c5t}
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 out=$R/gpurun_out
-P="python3 $R/bench.py --warmup 1 --no-cpu-baseline --no-shards --cons-steps 3 --steps 3"
+P="python3 $R/bench.py --full --warmup 1 --no-cpu-baseline --no-shards --cons-steps 3 --steps 3"
 cmd_for() {
   case $1 in
     c1|c2|c3|c4) echo "$P --only-solve $1" ;;
@@ -23,7 +23,7 @@ cmd_for() {
 }
 if [ -z "$NO_TRACE" ]; then  # NO_TRACE=1: only the per-workload passes (a second call for the remaining workloads)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_trace -o run -- \
-  python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/prof_${tag}_trace.log 2>&1 || exit $?
+  python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/prof_${tag}_trace.log 2>&1 || exit $?
 fi
 for w in $W; do
   C=$(cmd_for $w)

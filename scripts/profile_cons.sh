@@ -5,7 +5,7 @@ set -o pipefail
 tag=${1:-cons}
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-B="python3 $R/bench.py --only-consolidation --cons-steps 3 --warmup 1 --no-cpu-baseline"
+B="python3 $R/bench.py --full --only-consolidation --cons-steps 3 --warmup 1 --no-cpu-baseline"
 out=$R/gpurun_out
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_trace -o run -- $B > $out/prof_${tag}_trace.log 2>&1 || exit $?
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/prof_${tag}_fetch -o run -- $B > $out/prof_${tag}_fetch.log 2>&1 || exit $?

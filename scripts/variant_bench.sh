@@ -4,7 +4,7 @@
 mkdir -p gpurun_out
 for v in "$@"; do
   echo "=== variant '${v}'"
-  KS_LIB_VARIANT="$v" timeout -k 10 300 python -u bench.py --only-consolidation --no-cpu-baseline --no-c5 --no-shards \
+  KS_LIB_VARIANT="$v" timeout -k 10 300 python -u bench.py --full --only-consolidation --no-cpu-baseline --no-c5 --no-shards \
     > "gpurun_out/vb_${v:-main}.json" 2> "gpurun_out/vb_${v:-main}.err"
   rc=$?
   python - "gpurun_out/vb_${v:-main}.json" <<'EOF'
