@@ -197,7 +197,10 @@ int ks_cons_decide(ks_cons* c, const void* records, int world, int flags, const 
  * that advances sim_seconds per simulation the sequential replay consults: the multi-node search returns
  * its last saved command once the clock passes its timeout, the single-node scan abandons with no command.
  * The GPU has already run every simulation, so sim_seconds models the reference's per-simulation cost
- * (0: no timeout ever fires, which is ks_cons_decide). */
+ * (0: no timeout ever fires, which is ks_cons_decide).
+ * rs_table is the same table as for ks_cons_decide: its rows are in ks_cons_needed_sims order, and that order
+ * does not depend on the clock (ks_cons_needed_sims has none).  A clock only stops the search or the scan early,
+ * so the clocked replay reads a subset of those rows; the rows of simulations it never consults are ignored. */
 typedef struct ks_cons_clock {
   double multi_timeout_s;
   double single_timeout_s;

@@ -2742,9 +2742,9 @@ int ks_cons_validate(ks_cons* c, const char* command_json, size_t len, const ks_
 }
 
 // The simulations whose NewNodeClaims[0] requirement record the decision output needs, in the order
-// ks_cons_decide consumes them (a dry run of the replay that records every lookup).
-static std::vector<int> needed_sims(const ks_cons& c, const RecView& recs, int world, bool allSims,
-                                    const ks_cons_clock* clk = nullptr) {
+// ks_cons_decide consumes them (a dry run of the replay that records every lookup).  No clock: the list is the
+// clockless replay's (c.walk must be the clockless search), a clocked replay reads a subset of it.
+static std::vector<int> needed_sims(const ks_cons& c, const RecView& recs, int world, bool allSims) {
   std::vector<int> need;
   std::set<int> seen;
   std::vector<uint32_t> zero(std::max(c.pb->host.dims.RSW, 1), 0);
@@ -2754,7 +2754,7 @@ static std::vector<int> needed_sims(const ks_cons& c, const RecView& recs, int w
         if (seen.insert(sim).second) need.push_back(sim);
         return zero.data();
       },
-      false, clk);
+      false, nullptr);
   return need;
 }
 
@@ -2803,9 +2803,9 @@ int ks_cons_decide_clock(ks_cons* c, const void* records, int world, int flags, 
   c->check_usable();
   DeviceGuard guard(c->pb->device, nullptr);  // (carried probes run on the handle's GPU)
   const RecView recs = host_records(c, records, world);
-  carry_walk(*c, recs, world, clock);
   const bool all_sims = (flags & KS_CONS_ALL_SIMS) != 0;
   if (!rs_table && world == 1 && c->L.lworld == 1) {
+    carry_walk(*c, recs, world, clock);
     // One rank ran every simulation: the requirement records the output needs are read from this handle's
     // launch as the replay reaches them (one pass over the records, no needed_sims dry run).
     const int RSW = c->pb->host.dims.RSW;
@@ -2827,10 +2827,16 @@ int ks_cons_decide_clock(ks_cons* c, const void* records, int world, int flags, 
                            .c_str());
     return KS_OK;
   }
-  std::vector<int> need = needed_sims(*c, recs, world, all_sims, clock);
+  // rs_table's rows are in ks_cons_needed_sims order, and that list has no clock: it comes from the clockless
+  // search (needed_sims' dry run reads c->walk), whatever `clock` is.  A clock only shortens the search or the
+  // single-node scan, so the clocked replay reads a subset of these rows; mapping the table by a clocked dry run
+  // would hand every row after a probe the clock skipped to another simulation.
+  carry_walk(*c, recs, world, nullptr);
+  std::vector<int> need = needed_sims(*c, recs, world, all_sims);
   if (!need.empty() && !rs_table) throw KsError(KS_ERR_ARG, "requirement records of the needed simulations missing");
   std::map<int, const uint32_t*> table;
   for (size_t i = 0; i < need.size(); i++) table[need[i]] = rs_table + i * c->pb->host.dims.RSW;
+  carry_walk(*c, recs, world, clock);  // (the cached walk when clock is null)
   *json_out = strdup(decide_json(*c, recs, world, all_sims, [&](int sim) { return table.at(sim); },
                                  (flags & KS_CONS_CANDIDATES) != 0, clock, (flags & KS_CONS_NO_SIMS) == 0)
                          .c_str());

@@ -29,10 +29,11 @@ def _host_staged():
     return dist.get_backend() == "gloo"
 
 
-def sharded_pass(c, rank, world, device, bufs, all_sims=False, candidates=False, sims=False):
+def sharded_pass(c, rank, world, device, bufs, all_sims=False, candidates=False, sims=False, clock=None):
     """Run rank `rank`'s simulations, exchange the records and the needed requirement records, decide on rank 0
-    (all_sims / candidates / sims: Consolidator.decide's flags).  Returns (kernel ms, gathered records as bytes,
-    decision or None on the other ranks)."""
+    (all_sims / candidates / sims / clock: Consolidator.decide's flags and virtual clock; the table exchanged is
+    the clockless one whatever the clock, ks_cons_needed_sims has none).  Returns (kernel ms, gathered records as
+    bytes, decision or None on the other ranks)."""
     _, ms = c.run(rank, world, device=device, out_ptr=bufs.out.data_ptr())
     if _host_staged():
         out = bufs.out.cpu()
@@ -55,5 +56,6 @@ def sharded_pass(c, rank, world, device, bufs, all_sims=False, candidates=False,
         table = {s: host[i * rsw:(i + 1) * rsw].tobytes() for i, s in enumerate(need)}
     doc = None
     if rank == 0:
-        doc = c.decide(recs, world, all_sims=all_sims, fetch=table.__getitem__, candidates=candidates, sims=sims)
+        doc = c.decide(recs, world, all_sims=all_sims, fetch=table.__getitem__, candidates=candidates, sims=sims,
+                       clock=clock)
     return ms, recs, doc

@@ -5,8 +5,16 @@
  *   abi_check solve <snapshot.json>     ks_problem_create + ks_solve, then every structured accessor
  *                                       (ks_results_nodeclaim / _requests / _requirements /
  *                                       existing nodes / pod errors) printed as one JSON document
+ *   abi_check consolidate <snapshot.json> WORLD FLAGS MULTI SINGLE SIM_SECONDS
+ *                                       one consolidation pass sharded over WORLD (<= 3) handles in this
+ *                                       process, as the header describes it: ks_cons_run per rank into one
+ *                                       [rank][slot] host buffer, ks_cons_needed_sims (sized by a first call),
+ *                                       the requirement table read from the owners, ks_cons_decide_clock with
+ *                                       the clock (MULTI, SINGLE, SIM_SECONDS) on rank 0's handle; a negative
+ *                                       SIM_SECONDS means plain ks_cons_decide.  Prints the decision JSON.
  *
- * tests/test_abi_c.py builds it and checks the solve output against ks_results_json's document. */
+ * tests/test_abi_c.py builds it and checks the solve output against ks_results_json's document and the
+ * consolidate output against the oracle. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -46,9 +54,72 @@ static int fail(const char* what, int rc) {
   return 1;
 }
 
+#define MAX_WORLD 3
+
+/* args: WORLD FLAGS MULTI SINGLE SIM_SECONDS */
+static int consolidate(const char* snap, size_t len, char** args) {
+  const int world = atoi(args[0]), flags = atoi(args[1]);
+  ks_cons_clock clk;
+  clk.multi_timeout_s = strtod(args[2], NULL);
+  clk.single_timeout_s = strtod(args[3], NULL);
+  clk.sim_seconds = strtod(args[4], NULL);
+  if (world < 1 || world > MAX_WORLD) {
+    fprintf(stderr, "WORLD must be 1..%d\n", MAX_WORLD);
+    return 2;
+  }
+  int rc;
+  ks_cons* h[MAX_WORLD] = {NULL, NULL, NULL};
+  for (int r = 0; r < world; r++)
+    if ((rc = ks_cons_create(snap, len, &h[r])) != KS_OK) return fail("ks_cons_create", rc);
+  /* the gathered records: [rank][slot], records_per_rank slots of record_bytes each */
+  const size_t per = (size_t)ks_cons_records_per_rank(h[0], world), rb = (size_t)ks_cons_record_bytes(h[0]);
+  char* recs = (char*)calloc((size_t)world * per * rb + 1, 1);
+  if (!recs) return fail("calloc", 0);
+  ks_solve_opts opts;
+  memset(&opts, 0, sizeof opts);
+  opts.device = -1;
+  opts.simulation_mode = 1;
+  opts.replicas = 1;
+  for (int r = 0; r < world; r++) {
+    double ms = 0;
+    if ((rc = ks_cons_run(h[r], r, world, &opts, recs + (size_t)r * per * rb, 0, &ms)) != KS_OK)
+      return fail("ks_cons_run", rc);
+  }
+  /* the simulations whose requirement records the output renders: the return value is the full count */
+  int32_t first = -1;
+  const int n = ks_cons_needed_sims(h[0], recs, world, flags, &first, 1);
+  if (n < 0) return fail("ks_cons_needed_sims", n);
+  int32_t* need = (int32_t*)calloc((size_t)n + 1, sizeof *need);
+  if (!need) return fail("calloc", 0);
+  if ((rc = ks_cons_needed_sims(h[0], recs, world, flags, need, n)) != n) return fail("ks_cons_needed_sims (2nd call)", rc);
+  if (n > 0 && need[0] != first) return fail("ks_cons_needed_sims order", 0);
+  /* the table, in that order; each row is read from the handle of the rank that ran the simulation */
+  const size_t rsw = (size_t)ks_cons_requirement_words(h[0]);
+  uint32_t* table = (uint32_t*)calloc(((size_t)n + 1) * (rsw + 1), sizeof *table);
+  if (!table) return fail("calloc", 0);
+  for (int i = 0; i < n; i++)
+    if ((rc = ks_cons_claim_requirements(h[need[i] % world], need[i], table + (size_t)i * rsw)) != KS_OK)
+      return fail("ks_cons_claim_requirements", rc);
+  char* js = NULL;
+  if (clk.sim_seconds < 0)
+    rc = ks_cons_decide(h[0], recs, world, flags, table, &js);
+  else
+    rc = ks_cons_decide_clock(h[0], recs, world, flags, table, &clk, &js);
+  if (rc != KS_OK) return fail("ks_cons_decide", rc);
+  printf("%s\n", js);
+  ks_free(js);
+  free(table);
+  free(need);
+  free(recs);
+  for (int r = 0; r < world; r++) ks_cons_free(h[r]);
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  if (argc != 3) {
-    fprintf(stderr, "usage: %s inspect|solve <snapshot.json>\n", argv[0]);
+  const int cons = argc == 8 && strcmp(argv[1], "consolidate") == 0;
+  if (argc != 3 && !cons) {
+    fprintf(stderr, "usage: %s inspect|solve <snapshot.json>\n       %s consolidate <snapshot.json> WORLD FLAGS MULTI SINGLE SIM_SECONDS\n",
+            argv[0], argv[0]);
     return 2;
   }
   size_t len = 0;
@@ -58,6 +129,11 @@ int main(int argc, char** argv) {
     return 2;
   }
   int rc;
+  if (cons) {
+    rc = consolidate(snap, len, argv + 3);
+    free(snap);
+    return rc;
+  }
   if (strcmp(argv[1], "inspect") == 0) {
     char* dims = NULL;
     if ((rc = ks_problem_inspect(snap, len, &dims)) != KS_OK) return fail("ks_problem_inspect", rc);

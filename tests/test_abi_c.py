@@ -81,3 +81,30 @@ def test_c_client_bounds_requirements(tmp_path):
     want = Scheduler(json.dumps(snap)).solve().canonical()
     for c, w in zip(got["newNodeClaims"], want["newNodeClaims"]):
         assert [_req_string(q) for q in c["requirements"]] == w["requirements"]
+
+
+@pytest.mark.gpu
+def test_c_client_consolidates_like_the_oracle(tmp_path):
+    """One consolidation pass driven from C as include/karpenter_amd.h describes it (the contract a cgo shim
+    binds): WORLD handles, ks_cons_run per rank into one [rank][slot] buffer, ks_cons_needed_sims sized by a first
+    call, the requirement table read from the owners in that order, ks_cons_decide / ks_cons_decide_clock.  The
+    table's order has no clock: under (0, 1000, 1) and (2, 1000, 1) the multi-node search stops before probes
+    whose rows are in the table (decide_cases.SHIFT).  Decision == oracle, every field."""
+    import decide_cases as dc
+
+    if not os.path.exists(EXE):
+        build()
+    bad = []
+    for name in ("shift-305", "replace"):
+        path = tmp_path / (name + ".json")
+        path.write_text(dc.snapshot(name))
+        for world in (1, 2):
+            for clock in (None, (0.0, 1000.0, 1.0), (2.0, 1000.0, 1.0)):
+                args = [str(x) for x in (clock or (0.0, 0.0, -1.0))]
+                out = subprocess.run([EXE, "consolidate", str(path), str(world), "2"] + args, capture_output=True,
+                                     text=True, timeout=120)
+                assert out.returncode == 0, out.stderr
+                d = dc.first_diff(dc.oracle(name, clock), json.loads(out.stdout))
+                if d is not None:
+                    bad.append("%s world %d clock %r: %s" % (name, world, clock, d))
+    assert not bad, "\n".join(bad)

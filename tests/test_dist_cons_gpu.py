@@ -34,6 +34,9 @@ def _snapshot(kind):
     return json.dumps(cs.random_cluster(4, topology=False) if kind == "carry" else cs.make("late-carry", 0))
 
 
+CLOCKED = ("shift-305", (0.0, 1000.0, 1.0))  # decide_cases: the clock stops the search before probes the table lists
+
+
 def _worker(rank, world, port, kind, q):
     import sys
 
@@ -47,6 +50,18 @@ def _worker(rank, world, port, kind, q):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
+        if kind == "clocked":
+            import decide_cases as dc
+
+            c = Consolidator(dc.snapshot(CLOCKED[0]))
+            bufs = ShardBuffers(c, world, "cuda:0")
+            _, recs, got = sharded_pass(c, rank, world, 0, bufs, all_sims=False, candidates=True, sims=True,
+                                        clock=CLOCKED[1])
+            if rank == 0:
+                want = dc.oracle(CLOCKED[0], CLOCKED[1])
+                q.put((json.dumps(got, sort_keys=True), json.dumps(want, sort_keys=True), dc.first_diff(want, got)))
+            dist.barrier()
+            return
         snap = _snapshot(kind)
         c = Consolidator(snap)
         bufs = ShardBuffers(c, world, "cuda:0")
@@ -83,3 +98,24 @@ def test_multiprocess_sharded_pass_decides_like_one_process(world, kind):
         assert nneed > 0  # the decision renders replacement requirements another rank's GPU holds
     else:
         assert any(p["carried"] for p in doc["multi"]["path"])
+
+
+def test_multiprocess_sharded_pass_under_a_clock():
+    """World 2, sharded_pass(clock=...): the table is exchanged in ks_cons_needed_sims order (no clock) and rank 0
+    replays under a clock that stops the multi-node search after one probe.  Rank 0's document == the oracle's."""
+    import torch.multiprocessing as mp
+
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, "clocked", q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got, want, diff = q.get(timeout=150)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert got == want, diff
+    doc = json.loads(want)
+    assert len(doc["multi"]["path"]) == 1 and doc["single"]["command"]["action"] == "replace"
