@@ -69,7 +69,9 @@ int ks_problem_encode_binary(const char* snapshot_json, size_t len, void** buf, 
 int ks_problem_check_binary(const void* buf, size_t len);
 
 /* Host-only encode of a snapshot (no device needed): returns JSON with the universe sizes (keys,
- * value words, resources, instance types, relaxation states).  Diagnostics / CPU tests. */
+ * value words, resources "R", instance types, relaxation states), "lean" / "negReq" (resource-only pods /
+ * some negative request) and "plans" (the LDS plan at the default and a few reduced budgets).
+ * Diagnostics / CPU tests. */
 int ks_problem_inspect(const char* snapshot_json, size_t len, char** dims_json);
 
 /* Solve (scheduler.go:140-189) on the GPU.  Fresh scheduler state every call (a Scheduler is
@@ -79,7 +81,13 @@ void ks_results_free(ks_results* r);
 
 /* Results as canonical JSON: {"newNodeClaims":[{nodePoolName, hostname, pods[], instanceTypeOptions[],
  * requests{}, requirements[], requirementsString}], "existingNodes":[{name, pods[]}],
- * "podErrors":{"<pod index>": "<error text>"}}.  Free with ks_free. */
+ * "podErrors":{"<pod index>": "<error text>"}, "stats":{<solve counters>, "route":{...}}}.
+ * "stats"."route" names the k_solve instantiation the Solve launched: {"family": "solve" | "solve_topo",
+ * "rt": 3 | 4 | 0 (the live-resource count the kernel is specialised for; 0: the generic code, any count),
+ * "tl": 0 | 1 (instance-type tables LDS-resident), "lean": 0 | 1 (the resource-only instantiation),
+ * "n": work items, "launches": [the same fields for every launch of this Solve, in order]}.  A Solve that
+ * re-plans (a lean Solve leaving for the non-lean code, a wider NodeClaim plan) has one entry per launch;
+ * the outer fields are the last launch's.  Free with ks_free. */
 int ks_results_json(const ks_results* r, char** json_out);
 
 /* Structured accessors for a cgo shim (no JSON on the hot return path). */
@@ -141,7 +149,8 @@ int ks_cons_create(const char* snapshot_json, size_t len, ks_cons** out);
  * simulation plan), as for ks_problem_save / ks_problem_create_binary. */
 int ks_cons_save(const ks_cons* c, void** buf, size_t* len);
 int ks_cons_create_binary(const void* buf, size_t len, ks_cons** out);
-/* Host-only (no device): JSON {candidates:[{name, disruptionCost, pods}], sims, multiPrefixes, recordBytes}. */
+/* Host-only (no device): JSON {candidates:[{name, disruptionCost, pods}], sims, multiPrefixes, recordBytes,
+ * R, G, lean, negReq, simPlan:{KO, KL, talloc, tsort, lds}} (simPlan: the LDS plan of a world-1 pass). */
 int ks_cons_inspect(const char* snapshot_json, size_t len, char** out_json);
 /* Cluster-state events between two passes against the resident handle (replaces re-reading the cluster
  * and rebuilding the scheduler per pass: state/cluster.go:220-512 UpdatePod/DeletePod/DeleteNode,
@@ -229,6 +238,13 @@ int ks_cons_sim_counters_n(ks_cons* c, int sim, int64_t* out, int n);
  * (multinodeconsolidation.go:111-114, helpers.go:102-104, preferences.go:60-147): a probe holding such a pod is
  * re-simulated from the carried relaxation states, one launch per probe (typically none). */
 int ks_cons_last_reruns(const ks_cons* c);
+/* The k_solve launches since this handle's last ks_cons_run began, in order, as a JSON list of
+ * {"family": "sims" | "sims_topo" | "sims_mw" | "sims_mixed", "rt", "tl", "lean", "n"} (as "stats"."route" of
+ * ks_results_json; "sims_mixed" adds "nmw", its leading simulations on 4-wave workgroups): the pass's own
+ * launches (two when the long simulations run on a second stream, or a topology plan launches in two phases),
+ * then one per carried-probe re-run of ks_cons_decide / ks_cons_needed_sims and per ks_cons_validate.
+ * Free with ks_free. */
+int ks_cons_last_routes(const ks_cons* c, char** json_out);
 /* Algorithmic bytes the gathered simulations scanned, summed from their records. */
 double ks_cons_records_alg_bytes(const ks_cons* c, const void* records, int world);
 

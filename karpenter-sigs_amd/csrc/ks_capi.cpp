@@ -20,6 +20,25 @@ using namespace ks;
 static thread_local std::string g_err;
 namespace ks {
 void set_last_error(const std::string& m) { g_err = m; }
+
+static thread_local std::vector<Route>* g_routes = nullptr;
+void route_note(const Route& r) {
+  if (g_routes) g_routes->push_back(r);
+}
+RouteScope::RouteScope(std::vector<Route>* log) : prev(g_routes) { g_routes = log; }
+RouteScope::~RouteScope() { g_routes = prev; }
+static std::string route_json(const Route& r) {
+  static const char* fam[] = {"solve", "solve_topo", "sims", "sims_topo", "sims_mw", "sims_mixed"};
+  std::string o = std::string("{\"family\":\"") + fam[r.family] + "\",\"rt\":" + std::to_string(r.rt) +
+                  ",\"tl\":" + std::to_string(r.tl) + ",\"lean\":" + std::to_string(r.lean) + ",\"n\":" + std::to_string(r.n);
+  if (r.family == KR_SIMS_MIXED) o += ",\"nmw\":" + std::to_string(r.nmw);
+  return o + "}";
+}
+std::string routes_json(const std::vector<Route>& log) {
+  std::string o = "[";
+  for (size_t i = 0; i < log.size(); i++) o += (i ? "," : "") + route_json(log[i]);
+  return o + "]";
+}
 }  // namespace ks
 
 namespace {
@@ -166,6 +185,7 @@ struct ks_results {
     }
   };
   ks_problem* pb = nullptr;  // a reference on the problem the lazy rendering reads (ks_problem_free defers)
+  std::vector<ks::Route> routes;  // the k_solve launches of this Solve, in order (a re-plan adds one)
   // First-use rendering writes the claims' caches: serialised, so two threads reading one Results (ctypes
   // and cgo release the interpreter / scheduler around the call) render once; what a call hands out is
   // never rebuilt afterwards.
@@ -1083,6 +1103,7 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   long long nlate = 0;
   for (uint64_t x : h.tab.tg_late) nlate += __builtin_popcountll(x);
   kv("lateGroups", nlate); kv("groupWords", d.GMW); kv("unlabelledNodes", d.tgUnlab);
+  kv("lean", d.lean); kv("negReq", d.negReq);
   long long nfail = 0, nshared = 0, nverr = 0;
   for (char x : h.injectFailed) nfail += x ? 1 : 0;
   for (int32_t f : h.tab.pod_flags) {
@@ -1158,6 +1179,8 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   // caller pays both launches, so the reported times are their sums (the re-plan is remembered).
   float ms = 0, setup = 0, fms = 0, fnms = 0;
   int feasLaunches = 0, attempts = 0;
+  std::vector<Route> routes;
+  RouteScope routeScope(&routes);
   for (int attempt = 0; attempt < 4; attempt++) {
     attempts++;
     HIPCHK(hipEventRecord(e0, pb->stream));
@@ -1217,6 +1240,7 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   } else {
     r = collect(pb, w0);
   }
+  r->routes = routes;
   r->kernel_ms = ms;
   r->solve_ms = ms - setup;
   r->feas_ms = fms;
@@ -1260,6 +1284,11 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "runs", "runPods", "sortsExact", "fineTopoPop", "fineState", "fineRefill",
                                 "fineWindowTests", "fineWindowBlocks", "fineRecord", "fineNodeCommit", "fineWindowTopo"};
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);
+  // the launched k_solve instantiation: the last launch's fields, and every launch of this Solve in order
+  if (!r->routes.empty()) {
+    std::string last = routes_json({r->routes.back()});
+    o += ",\"route\":" + last.substr(1, last.size() - 3) + ",\"launches\":" + routes_json(r->routes) + "}";
+  }
   o += "}}";
   *json_out = strdup(o.c_str());
   return KS_OK;

@@ -348,6 +348,9 @@ struct ks_cons {
   Walk walk;
   uint64_t passId = 0;  // ks_cons_run calls (a walk is valid for the pass it was computed on)
   Launch LR;            // the re-runs' launch (its buffers are kept between re-runs)
+  // the k_solve launches since the last ks_cons_run began, in order: the pass's (both streams of a split or a
+  // two-phase topology plan), then those of the carried-probe re-runs and of validate() (ks_cons_last_routes)
+  std::vector<Route> routes;
 
   int sim_of_multi(int mid) const { return multiHi - mid; }  // mid in [1, multiHi]
   int sim_of_single(int i) const { return multiHi + i; }
@@ -860,6 +863,17 @@ std::vector<int32_t> sim_topology(const ks_cons& c, const ks_cons::Sim& sm, cons
   return out;
 }
 
+// A pass's LDS plan: a small budget per simulation so several simulations share a CU.  A pass with topology is
+// bound by its longest simulation (a multi-node prefix), not by throughput: its simulations get room for the
+// instance-type tables in LDS (TL) at the price of fewer resident per CU.  maxP: the longest simulation's pods.
+Plan sim_plan(const KsDims& d, int maxP) {
+  KsDims dd = d;
+  dd.Kcap = std::max(1, std::min(maxP, 16384));
+  Plan pl = make_plan(dd, d.G ? 64 * 1024 : 40 * 1024, true);
+  if (pl.lds > 80 * 1024 || pl.KO < 1) pl = make_plan(dd, 160 * 1024 - 256, true);
+  return pl;
+}
+
 // Build and upload the launch of this rank's simulations (cached per (rank, world)).
 void prepare_launch(ks_cons& c, int rank, int world) {
   if (c.L.lrank == rank && c.L.lworld == world) return;
@@ -1229,13 +1243,7 @@ void prepare_launch(ks_cons& c, int rank, int world) {
   if (ai.total) HIPCHK(hipMemcpy(ibase, stage.data(), ai.total, hipMemcpyHostToDevice));
   if (ns) HIPCHK(hipMemcpy(c.L.lworks, works.data(), sizeof(KsWork) * ns, hipMemcpyHostToDevice));
   c.L.lhost = works;
-  // LDS plan: a small budget per simulation so several simulations share a CU.  A pass with topology is bound by
-  // its longest simulation (a multi-node prefix), not by throughput: its simulations get room for the
-  // instance-type tables in LDS (TL) at the price of fewer resident per CU.
-  KsDims dd = d;
-  dd.Kcap = std::max(1, std::min(maxP, 16384));
-  c.L.lplan = make_plan(dd, d.G ? 64 * 1024 : 40 * 1024, true);
-  if (c.L.lplan.lds > 80 * 1024 || c.L.lplan.KO < 1) c.L.lplan = make_plan(dd, 160 * 1024 - 256, true);
+  c.L.lplan = sim_plan(d, maxP);
   if (c.L.lplan.lds > 160 * 1024 || c.L.lplan.KO < 1) throw KsError(KS_ERR_CAPACITY, "simulation state does not fit in LDS");
   // Simulations of at least 256 pods (the multi-node prefixes lead the plan) get 4-wave workgroups in one
   // mixed launch when the plan is chain-bound: its pods number at most kMwChainRatio times its longest
@@ -1641,6 +1649,7 @@ namespace {
 // Returns the HIP-event time of both launches on the stream they ran on.
 double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice) {
   PhaseTimer pt("run_sims");
+  RouteScope routeScope(&c.routes);
   prepare_launch(c, rank, world);
   ks_problem& pb = *c.pb;
   const int ns = (int)c.L.lsims.size();
@@ -2506,6 +2515,19 @@ std::string inspect_json(const ks_cons& c, bool nodes) {
     o += "]";
     if (h.dims.G) o += ",\"topology\":" + topology_json(c);
   }
+  // the world-1 pass's LDS plan (prepare_launch: sim_plan over the longest simulation's pods) and the dimensions
+  // that pick its k_solve instantiation
+  int maxP = 1;
+  for (const ks_cons::Sim& sm : c.sims) {
+    size_t n = c.pending.size() + c.deleting.size();
+    for (int ci : sm.cands) n += c.cands[(size_t)ci].pods.size();
+    maxP = std::max(maxP, (int)n);
+  }
+  const Plan pl = sim_plan(h.dims, maxP);
+  o += ",\"R\":" + std::to_string(h.dims.R) + ",\"G\":" + std::to_string(h.dims.G) + ",\"lean\":" +
+       std::to_string(h.dims.lean) + ",\"negReq\":" + std::to_string(h.dims.negReq) + ",\"simPlan\":{\"KO\":" +
+       std::to_string(pl.KO) + ",\"KL\":" + std::to_string(pl.KL) + ",\"talloc\":" + std::to_string(pl.talloc) +
+       ",\"tsort\":" + std::to_string(pl.tsort) + ",\"lds\":" + std::to_string(pl.lds) + "}";
   o += ",\"sims\":" + std::to_string(c.sims.size()) + ",\"multiPrefixes\":" + std::to_string(c.multiHi) +
        ",\"recordBytes\":" + std::to_string(4 * c.recWords) + ",\"pods\":" + std::to_string(h.dims.P) +
        ",\"nodes\":" + std::to_string(h.dims.N) + ",\"groups\":" + std::to_string(h.dims.G) +
@@ -2723,6 +2745,7 @@ int ks_cons_run(ks_cons* c, int rank, int world, const ks_solve_opts* opts, void
   c->check_usable();
   DeviceGuard guard(c->pb->device, opts);
   c->passId++;  // (a decision's multi-node search is re-resolved for the new records)
+  c->routes.clear();
   const double ms = run_sims(*c, rank, world, records, records_on_device != 0);
   if (kernel_ms) *kernel_ms = ms;
   return KS_OK;
@@ -2865,6 +2888,14 @@ int ks_cons_sim_counters_n(ks_cons* c, int sim, int64_t* out, int n) {
 }
 
 int ks_cons_last_reruns(const ks_cons* c) { return c && c->walk.valid ? c->walk.reruns : -1; }
+
+int ks_cons_last_routes(const ks_cons* c, char** json_out) {
+  API_TRY
+  if (!c || !json_out) throw KsError(KS_ERR_ARG, "null argument");
+  *json_out = strdup(routes_json(c->routes).c_str());
+  return KS_OK;
+  API_CATCH
+}
 
 double ks_cons_records_alg_bytes(const ks_cons* c, const void* records, int world) {
   if (!c || world < 1 || (!records && !(world == 1 && c->L.lworld == 1 && (c->L.hdrOnly || c->L.keptFull)))) return 0;

@@ -96,6 +96,19 @@ struct Plan {
   uint64_t lds;    // dynamic LDS bytes
 };
 
+// The k_solve instantiation one launch picked (ks_solve.hip: launch_family, launch_sims_mw, launch_sims_mixed),
+// noted on the host at the launch site for the caller's route log (ks_runtime.h RouteScope).
+enum RouteFamily { KR_SOLVE = 0, KR_SOLVE_TOPO, KR_SIMS, KR_SIMS_TOPO, KR_SIMS_MW, KR_SIMS_MIXED };
+struct Route {
+  int32_t family;  // RouteFamily
+  int32_t rt;      // the RT template argument: 3, 4, or 0 (the generic code)
+  int32_t tl;      // TL: the instance-type tables are LDS-resident
+  int32_t lean;    // LEAN
+  int32_t n;       // work items (Solve replicas / simulations) of the launch
+  int32_t nmw;     // KR_SIMS_MIXED: the leading simulations on 4-wave workgroups (0 otherwise)
+};
+void route_note(const Route& r);  // host; a no-op outside a RouteScope
+
 // Device view (all pointers into one HBM allocation).
 struct KsDev {
   KsDims d;

@@ -53,6 +53,18 @@ struct Arena {
 };
 
 void set_last_error(const std::string& m);
+
+// The route log: while a RouteScope lives, every k_solve launch this thread makes (route_note, ks_problem.h)
+// is appended to its vector.  Scopes nest; the innermost one receives the notes.
+struct RouteScope {
+  std::vector<Route>* prev;
+  explicit RouteScope(std::vector<Route>* log);
+  ~RouteScope();
+  RouteScope(const RouteScope&) = delete;
+  RouteScope& operator=(const RouteScope&) = delete;
+};
+// [{"family":"sims_mixed","rt":4,"tl":1,"lean":1,"n":47,"nmw":3}, ...] ("nmw" for sims_mixed only)
+std::string routes_json(const std::vector<Route>& log);
 }  // namespace ks
 
 #define HIPCHK(x)                                                                                         \

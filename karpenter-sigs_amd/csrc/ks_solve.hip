@@ -2770,8 +2770,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256))) __attribute__((a
 // include this file), so the four compile in parallel.
 template <bool SIM, bool TOPO>
 hipError_t launch_family(const KsDev& D, const KsWork* works_dev, int n, const Plan& pl, hipStream_t st) {
-#define KS_LAUNCH(RT_, TL_, LEAN_) \
-  hipLaunchKernelGGL((k_solve<RT_, TL_, SIM, TOPO, LEAN_>), dim3(n), dim3(kWave), pl.lds, st, D, works_dev, pl)
+#define KS_LAUNCH(RT_, TL_, LEAN_)                                                                                 \
+  do {                                                                                                             \
+    route_note(Route{SIM ? (TOPO ? KR_SIMS_TOPO : KR_SIMS) : (TOPO ? KR_SOLVE_TOPO : KR_SOLVE), RT_, TL_, LEAN_, n, 0}); \
+    hipLaunchKernelGGL((k_solve<RT_, TL_, SIM, TOPO, LEAN_>), dim3(n), dim3(kWave), pl.lds, st, D, works_dev, pl); \
+  } while (0)
   if (n <= 0) return hipSuccess;  // e.g. a consolidation pass with no candidates: nothing to simulate
   const bool tl = pl.talloc != 0;
   // the lean instantiations exist for the common shapes only: 3 or 4 resources, LDS-resident tables
@@ -2809,6 +2812,7 @@ hipError_t launch_sims_mixed(const KsDev& D, const KsWork* w, int n, int nmw, co
   if (D.d.G || !D.d.lean || !pl.talloc || D.d.N <= 0 || lds > 160 * 1024) return hipErrorNotSupported;
   const int grid = nmw + (n - nmw + kMwWaves - 1) / kMwWaves;
   const dim3 blk(kMwWaves * kWave);
+  if (D.d.R == 3 || D.d.R == 4) route_note(Route{KR_SIMS_MIXED, D.d.R, 1, 1, n, nmw});
   switch (D.d.R) {
     case 3: hipLaunchKernelGGL((k_sim_mixed<3>), dim3(grid), blk, lds, st, D, w, pl, nmw, n, (int)stride); break;
     case 4: hipLaunchKernelGGL((k_sim_mixed<4>), dim3(grid), blk, lds, st, D, w, pl, nmw, n, (int)stride); break;
@@ -2822,6 +2826,7 @@ hipError_t launch_sims_mw(const KsDev& D, const KsWork* w, int n, const Plan& pl
   if (n <= 0) return hipSuccess;
   if (D.d.G || !D.d.lean || !pl.talloc || D.d.N <= 0 || pl.lds + kMwBytes > 160 * 1024) return hipErrorNotSupported;
   const dim3 blk(kMwWaves * kWave);
+  if (D.d.R == 3 || D.d.R == 4) route_note(Route{KR_SIMS_MW, D.d.R, 1, 1, n, 0});
   switch (D.d.R) {
     case 3: hipLaunchKernelGGL((k_solve<3, true, true, false, true, true>), dim3(n), blk, pl.lds + kMwBytes, st, D, w, pl); break;
     case 4: hipLaunchKernelGGL((k_solve<4, true, true, false, true, true>), dim3(n), blk, pl.lds + kMwBytes, st, D, w, pl); break;

@@ -379,6 +379,7 @@ def _cons_lib():
         l.ks_cons_records_alg_bytes.restype = ctypes.c_double
         l.ks_cons_last_reruns.argtypes = [vp]
         l.ks_cons_last_reruns.restype = ctypes.c_int
+        l.ks_cons_last_routes.argtypes = [vp, ctypes.POINTER(vp)]
         l._cons_ready = True
     return l
 
@@ -547,6 +548,14 @@ class Consolidator:
         """Multi-node probes the last decide() / needed_sims() re-simulated on this GPU from the pod objects
         earlier probes relaxed (ks_cons_last_reruns; -1: no decision yet)."""
         return _cons_lib().ks_cons_last_reruns(self._h)
+
+    @property
+    def last_routes(self):
+        """The k_solve launches since the last run() began, in order (ks_cons_last_routes): a list of
+        {"family", "rt", "tl", "lean", "n"[, "nmw"]}; re-runs of decide() and validate() append theirs."""
+        js = ctypes.c_void_p()
+        _check(_cons_lib().ks_cons_last_routes(self._h, ctypes.byref(js)))
+        return json.loads(_take_str(js))
 
     def alg_bytes(self, records, world=1):
         if records is None:

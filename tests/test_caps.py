@@ -63,3 +63,41 @@ def test_caps_parity(kind, seed):
     if kind == "pools":  # templates past the 32nd are used
         names = {t["metadata"]["name"] for t in snap["nodeClaimTemplates"][32:]}
         assert any(c["nodePoolName"] in names for c in want["newNodeClaims"]), "no claim from a template past 32"
+
+
+def _sixteen_names(seed=17):
+    import resource_cases as rc
+
+    return rc.with_resources(problems.random_problem(seed, n_pods=120, n_nodes=8), 12, seed)
+
+
+def test_sixteen_live_resource_names_encode():
+    """The cap itself: 16 names in the pods' requests (cpu, memory, pods, example.com/gpu and 12 more) fill every
+    index of the kernels' per-resource arrays."""
+    d = inspect(json.dumps(_sixteen_names()))
+    assert d["R"] == 16 and len(d["resources"]) == 16
+
+
+def test_seventeenth_live_resource_name_is_refused():
+    from karpenter_amd.scheduler import KsError
+
+    snap = _sixteen_names()
+    snap["pods"][5]["spec"]["containers"][0]["resources"]["requests"]["example.com/one-too-many"] = "1"
+    with pytest.raises(KsError) as e:
+        inspect(json.dumps(snap))
+    assert e.value.code == -3
+    assert "more than 16 resource names in the pods' / daemons' requests and the NodePool limits" in str(e.value)
+
+
+def test_seventeenth_name_nobody_requests_still_encodes():
+    """Capacity alone does not make a name live (Fits reads the candidate's names only)."""
+    snap = _sixteen_names()
+    for it in snap["instanceTypes"]:
+        it["capacity"]["example.com/unrequested"] = "4"
+    for n in snap["stateNodes"]:
+        n["capacity"]["example.com/unrequested"] = "4"
+        n["available"]["example.com/unrequested"] = "2"
+    d = inspect(json.dumps(snap))
+    assert d["R"] == 16 and "example.com/unrequested" not in d["resources"]
+    res = problems.canonical(bridge.solve(json.dumps(snap))[0])
+    assert res["newNodeClaims"] and res == problems.canonical(bridge.solve(json.dumps(_sixteen_names()))[0])

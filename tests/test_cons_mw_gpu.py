@@ -27,7 +27,9 @@ def _run(snap, env):
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
-        got = Consolidator(json.dumps(snap)).consolidate(all_sims=True)
+        c = Consolidator(json.dumps(snap))
+        got = c.consolidate(all_sims=True)
+        routes = c.last_routes
     finally:
         for k, v in old.items():
             if v is None:
@@ -35,7 +37,7 @@ def _run(snap, env):
             else:
                 os.environ[k] = v
     got.pop("kernel_ms")
-    return got
+    return got, routes
 
 
 @pytest.mark.gpu
@@ -44,7 +46,12 @@ def test_multi_wave_simulations_parity(seed, nodes, ppn, pending, nr, un):
     snap = synth.cluster_snapshot(nodes, ppn, n_its=60, seed=seed, n_pending=pending, not_ready_frac=nr,
                                   uninitialized_frac=un, spot_frac=0.3, it_range=(4, 40))
     want, _ = bridge.consolidate(json.dumps(snap), all_sims=True)
-    mw = _run(snap, {"KS_SIM_MW": "1", "KS_SIM_MW_MIN": "1"})
+    mw, routes = _run(snap, {"KS_SIM_MW": "1", "KS_SIM_MW_MIN": "1"})
     assert mw == want
-    single = _run(snap, {"KS_SIM_MW": "0"})
+    # these clusters have three live resources (cpu, memory, pods): one mixed launch of the rt = 3 instantiations,
+    # every simulation on a 4-wave workgroup (rt = 4: tests/test_route_matrix_gpu.py)
+    nsims = len(want["multi"]["sims"]) + len(want["single"]["sims"])
+    assert [(r["family"], r["rt"], r["tl"], r["lean"], r["n"], r["nmw"]) for r in routes] == [("sims_mixed", 3, 1, 1, nsims, nsims)]
+    single, routes = _run(snap, {"KS_SIM_MW": "0"})
     assert single == want
+    assert [(r["family"], r["rt"], r["tl"], r["lean"], r["n"]) for r in routes] == [("sims", 3, 1, 1, nsims)]
