@@ -70,9 +70,29 @@ int ks_problem_check_binary(const void* buf, size_t len);
 
 /* Host-only encode of a snapshot (no device needed): returns JSON with the universe sizes (keys,
  * value words, resources "R", instance types, relaxation states), "lean" / "negReq" (resource-only pods /
- * some negative request) and "plans" (the LDS plan at the default and a few reduced budgets).
+ * some negative request), "plans" (the LDS plan at the default and a few reduced budgets), "FNR" (relaxation
+ * states with label requirements: the rows of k_feasibility_nodes), "keyValues" (per key of "keyNames", the
+ * size of its value universe) and "coveredKeys" (the keys k_feasibility's rows decide).
  * Diagnostics / CPU tests. */
 int ks_problem_inspect(const char* snapshot_json, size_t len, char** dims_json);
+
+/* Test and diagnostic entry: read back one of the two static feasibility tables a Solve computes before
+ * k_solve.  which = 0: k_feasibility's pod-state x instance-type rows; which = 1: k_feasibility_nodes's
+ * pod-state x existing-node rows.  The call makes the launch a Solve makes, on the problem's stream, over
+ * the table filled with 0xA5 bytes (a word the kernel does not store reads back as 0xA5A5A5A5), waits for
+ * it and copies the table out; a later Solve rewrites the table as usual.  KS_ERR_UNSUPPORTED when the
+ * table is off for this problem (no pod label requirements, no existing nodes, KS_NO_FEASIBILITY /
+ * KS_NO_NODE_ROWS).
+ *   words (free with ks_free), n_words: which = 0: S * NTPL rows of TW words, row s * NTPL + t; bit p of a row
+ *     is position p of template t's instance-type list.  which = 1: FNR rows of ceil(N / 32) words, row
+ *     stateNodeRow[s]; bit n is existing node n in device order.
+ *   meta_json (free with ks_free): {"S", "NTPL", "TW", "N", "FNR", "podState0": [per pod, its first relaxation
+ *     state], "podNState": [per pod, the length of its chain], "stateNodeRow": [per state, its node row or -1],
+ *     "stateTolTpl": [per state, the bitmask of the templates whose taints it tolerates], "templates":
+ *     [{"instanceTypes": [names in position order], "irregular": [TW words: the positions whose instance
+ *     type holds a complement requirement]}], "nodes": [existing-node names in device order], "coveredKeys":
+ *     [the label keys the instance-type rows decide: those no instance type holds with more than one value]}. */
+int ks_problem_feasibility_rows(ks_problem* p, int which, char** meta_json, uint32_t** words, size_t* n_words);
 
 /* Solve (scheduler.go:140-189) on the GPU.  Fresh scheduler state every call (a Scheduler is
  * single-use in production, scheduler.go:49 is called per Schedule / per simulation). */

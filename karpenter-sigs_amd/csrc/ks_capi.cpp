@@ -1127,8 +1127,100 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   for (size_t i = 0; i < h.keyNames.size(); i++) { if (i) o += ","; ksjson::quote(o, h.keyNames[i]); }
   o += "],\"resources\":[";
   for (size_t i = 0; i < h.resNames.size(); i++) { if (i) o += ","; ksjson::quote(o, h.resNames[i]); }
+  // what the feasibility kernels' shapes depend on: the node rows (states with label requirements), the value
+  // universe of every key, and the keys k_feasibility's rows decide (no instance type holds two values)
+  long long fnr = 0;
+  for (int32_t f : h.tab.st_flags) fnr += (f & SF_HAS_KEYS) ? 1 : 0;
+  o += "],\"FNR\":" + std::to_string(fnr) + ",\"keyValues\":[";
+  for (size_t i = 0; i < h.keys.size(); i++) o += (i ? "," : "") + std::to_string(h.keys[i].nv);
+  o += "],\"coveredKeys\":[";
+  bool firstKey = true;
+  for (uint64_t m = d.itKeys & ~d.fkMulti; m; m &= m - 1) {
+    if (!firstKey) o += ",";
+    firstKey = false;
+    ksjson::quote(o, h.keyNames[(size_t)__builtin_ctzll(m)]);
+  }
   o += "]}";
   *out = strdup(o.c_str());
+  return KS_OK;
+  API_CATCH
+}
+
+// Test / diagnostic read-back of k_feasibility's (which = 0) or k_feasibility_nodes's (which = 1) table: the
+// launch a Solve makes, on the problem's stream, over a table filled with 0xA5 bytes first (a word the kernel
+// fails to store then reads back as the fill, not as whatever the allocation held), copied to the host.
+// meta_json indexes the words: instance-type row (s * NTPL + t) has TW words, node row st_fnrow[s] has
+// ceil(N / 32) words.
+int ks_problem_feasibility_rows(ks_problem* pb, int which, char** meta_json, uint32_t** words, size_t* n_words) {
+  API_TRY
+  if (!pb || !meta_json || !words || !n_words) throw KsError(KS_ERR_ARG, "null argument");
+  if (which != 0 && which != 1) throw KsError(KS_ERR_ARG, "which must be 0 (instance-type rows) or 1 (node rows)");
+  const Host& h = pb->host;
+  const auto& t = h.tab;
+  const KsDims& d = pb->dev.d;
+  if (!(which == 0 ? d.fmOn : d.fnOn))
+    throw KsError(KS_ERR_UNSUPPORTED, which == 0 ? "the instance-type rows are off for this problem"
+                                                 : "the node rows are off for this problem");
+  DeviceGuard guard(pb->device, nullptr);
+  const size_t NWN = ((size_t)d.N + 31) / 32;
+  const size_t n = which == 0 ? (size_t)d.S * d.NTPL * d.TW : (size_t)d.FNR * NWN;
+  uint32_t* dst = which == 0 ? pb->dev.st_fm : pb->dev.st_fn;
+  HIPCHK(hipMemsetAsync(dst, 0xA5, n * 4, pb->stream));
+  if (which == 0)
+    launch_feasibility(pb->dev, pb->stream);
+  else
+    launch_feasibility_nodes(pb->dev, pb->stream);
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> host;
+  dl(host, dst, n, pb->stream);
+  HIPCHK(hipStreamSynchronize(pb->stream));
+  std::string o = "{";
+  auto kv = [&](const char* k, long long v) { o += std::string(o.size() > 1 ? "," : "") + "\"" + k + "\":" + std::to_string(v); };
+  kv("S", d.S); kv("NTPL", d.NTPL); kv("TW", d.TW); kv("N", d.N); kv("FNR", d.FNR);
+  auto ints = [&](const char* k, size_t cnt, auto&& at) {
+    o += std::string(",\"") + k + "\":[";
+    for (size_t i = 0; i < cnt; i++) o += (i ? "," : "") + std::to_string(at(i));
+    o += "]";
+  };
+  ints("podState0", (size_t)d.P, [&](size_t i) { return (long long)t.pod_state0[i]; });
+  ints("podNState", (size_t)d.P, [&](size_t i) { return (long long)t.pod_nstate[i]; });
+  {
+    int row = 0;  // as ks_upload numbers them: one row per state with label requirements, in state order
+    ints("stateNodeRow", (size_t)d.S, [&](size_t s) { return (long long)((t.st_flags[s] & SF_HAS_KEYS) ? row++ : -1); });
+  }
+  ints("stateTolTpl", (size_t)d.S, [&](size_t s) { return (unsigned long long)t.st_toltpl[s]; });
+  o += ",\"templates\":[";
+  for (int tt = 0; tt < d.NTPL; tt++) {
+    const int tb = t.tpl_it_beg[(size_t)tt], cnt = t.tpl_it_beg[(size_t)tt + 1] - tb;
+    o += tt ? ",{\"instanceTypes\":[" : "{\"instanceTypes\":[";
+    for (int p = 0; p < cnt; p++) {
+      if (p) o += ",";
+      ksjson::quote(o, h.its[(size_t)t.tpl_its[(size_t)(tb + p)]].name);
+    }
+    o += "],\"irregular\":[";
+    const uint32_t* irr = &t.fk_words[(size_t)t.fk_tpl[(size_t)tt * 3 + 1]];
+    for (int w = 0; w < d.TW; w++) o += (w ? "," : "") + std::to_string(irr[w]);
+    o += "]}";
+  }
+  o += "],\"nodes\":[";
+  for (int i = 0; i < d.N; i++) {
+    if (i) o += ",";
+    ksjson::quote(o, h.nodes[(size_t)i].name);
+  }
+  o += "],\"coveredKeys\":[";
+  bool first = true;
+  for (uint64_t m = d.itKeys & ~d.fkMulti; m; m &= m - 1) {
+    if (!first) o += ",";
+    first = false;
+    ksjson::quote(o, h.keyNames[(size_t)__builtin_ctzll(m)]);
+  }
+  o += "]}";
+  uint32_t* buf = (uint32_t*)malloc(std::max<size_t>(n, 1) * 4);
+  if (!buf) throw KsError(KS_ERR_INTERNAL, "out of memory");
+  memcpy(buf, host.data(), n * 4);
+  *meta_json = strdup(o.c_str());
+  *words = buf;
+  *n_words = n;
   return KS_OK;
   API_CATCH
 }

@@ -82,6 +82,8 @@ def lib():
     l.ks_problem_encode_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp),
                                            ctypes.POINTER(ctypes.c_size_t)]
     l.ks_problem_check_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    l.ks_problem_feasibility_rows.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                              ctypes.POINTER(ctypes.c_size_t)]
     l.ks_cons_save.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
     l.ks_cons_create_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp)]
     l.ks_last_error.restype = ctypes.c_char_p
@@ -288,6 +290,20 @@ class Scheduler:
     def save(self):
         """The binary snapshot of the encoded problem (bytes)."""
         return _take_bytes(lib().ks_problem_save, self._h)
+
+    def feasibility_rows(self, which):
+        """Test / diagnostic read-back (ks_problem_feasibility_rows): which = 0 the pod-state x instance-type
+        rows, 1 the pod-state x existing-node rows, as the kernels a Solve launches write them.  Returns
+        (meta dict, words as a numpy uint32 array); KsError KS_ERR_UNSUPPORTED when the table is off."""
+        import numpy as np
+
+        meta, words, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        _check(lib().ks_problem_feasibility_rows(self._h, which, ctypes.byref(meta), ctypes.byref(words), ctypes.byref(n)))
+        try:
+            arr = np.frombuffer(ctypes.string_at(words, n.value * 4), dtype=np.uint32).copy()
+        finally:
+            lib().ks_free(words)
+        return json.loads(_take_str(meta)), arr
 
     def solve(self, replicas=1, device=-1, simulation_mode=True, timing_only=False, lds_budget=0):
         """Solve(ctx, pods) with fresh scheduler state; replicas>1 runs that many independent copies
