@@ -325,7 +325,10 @@ enum Counter {
   CT_SORT_EXACT,   // claim re-sorts that ran the lane-0 pdqsort (not the wave-parallel partialInsertionSort)
   CT_FINE,         // [8] diagnostic build: topo_pop, state record, window refill, window-block tests, window blocks
                    // tested (count), Topology.Record, simulation node commit, window-block tests' topology share
-  CT_NCOUNTERS = 35
+  CT_RUN_CROSS = CT_FINE + 8,  // LEAN Solve claim runs: re-sort crossings continued inside a step
+  CT_RUN_CROSS_STOPS,          // continuations refused: a position before the claim's new one passed the quick test
+  CT_RUN_CROSS_LOST,           // refusals after which the pod landed on the run's claim all the same (a step lost)
+  CT_NCOUNTERS = 38
 };
 // KE_LEAN_EXIT: a LEAN Solve of pods sharing a UID met its first push-back (the host re-runs it non-LEAN)
 enum KernelError { KE_OK = 0, KE_CLAIM_CAP = 1, KE_ITER_CAP = 2, KE_STACK = 3, KE_LEAN_EXIT = 4 };

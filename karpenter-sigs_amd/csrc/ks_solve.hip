@@ -46,6 +46,9 @@
 #ifndef KS_CLAIM_RUNS  // LEAN Solve: runs of identical pods placed on one NodeClaim in one step
 #define KS_CLAIM_RUNS 1
 #endif
+#ifndef KS_RUN_CROSS  // those runs stay on their NodeClaim across the re-sorts inside a step (0: end at each)
+#define KS_RUN_CROSS 1
+#endif
 
 #include "ks_gosort.h"
 #include "ks_problem.h"

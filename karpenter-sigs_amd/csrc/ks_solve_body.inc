@@ -274,6 +274,12 @@
   if (SIM && !ident) S.sim_queue_init(P);
   int wn = 0, wi = 0;  // window size / next index
   int64_t pops = 0, sorts = 0, slow = 0, exact = 0, windows = 0, fulls = 0, fullFails = 0, runs = 0, runPods = 0;
+  // LEAN Solve claim runs across re-sorts (KS_RUN_CROSS): crossings continued inside a step, continuations refused
+  // (a position before the claim's new one passed the quick test), and the refusals after which the pod landed
+  // on the run's claim all the same (the only ones that cost a step: any other ends the run anyway)
+  int64_t cross = 0, crossStops = 0, crossLost = 0;
+  int stopC = -1;                    // the claim of a continuation just refused
+  int64_t sortB = 0, pendSortB = 0;  // this add()'s re-sort bytes; those of a re-sort run for the next add()
   // Every pop either places a pod, relaxes it, or marks it stale; the reference's queue can cycle
   // O(P^2) in adversarial inputs, far beyond any realistic batch.  Bound it so a logic error ends the
   // kernel with KE_ITER_CAP instead of hanging the device.
@@ -519,6 +525,8 @@
     qlen--;
     if (++pops > popCap) { err = KE_ITER_CAP; break; }
     const int64_t abPop = S.algbytes;  // (claim runs: one pod's algorithmic bytes)
+    const int prevStop = stopC;        // (claim runs: the claim whose run the step before left to this pod's scan)
+    stopC = -1;
     const int s = rdl(w.s, wi);
     const int sflags = rdl(w.flags, wi);
     const uint64_t toltpl = (uint64_t)rdl64((int64_t)w.toltpl, wi);
@@ -822,10 +830,15 @@
     if (U(!placed && nclaims > 0)) {
       PH_BEGIN(t2);
       sorts++;
+      sortB = pendSortB;  // a re-sort the step before ran for this add() (KS_RUN_CROSS, a refused continuation)
+      S.algbytes += pendSortB;
+      pendSortB = 0;
       if (!U(srt)) {
+        const int64_t ab = S.algbytes;
         exact += S.sort_claims(nclaims);
         slow++;
         srt = true;
+        sortB += S.algbytes - ab;
       }
       PH_END(t2, 2);
       for (int base = 0; U(base < nclaims && !placed && !simNoClaim); base += kWave) {
@@ -856,7 +869,9 @@
               // was pushed back (ident) the queue is NewQueue's order and the run is the popped pod's run length
               // (launch_solve's sim_run_lengths), which may reach past the window; otherwise the identical,
               // non-stale pods that follow in the window.
-              if (srt && (ident || wi < wn)) {
+              // (KS_RUN_CROSS: a commit that left a descent enters too -- the run starts with the re-sort)
+              if (KS_RUN_CROSS && prevStop == c) crossLost++;  // the refused pod landed on the run's claim after all
+              if ((srt || KS_RUN_CROSS) && (ident || wi < wn)) {
                 int m;
                 if (ident) {
                   m = rdl(w.rl, wi - 1) - 1;
@@ -878,21 +893,101 @@
                 }
                 m = UI(m);
                 if (m > 0) {
-                  const int cj = uni(S.s_okey[jj]);
-                  const int nx = jj + 1 < nclaims ? uni(S.s_okey[jj + 1]) : 0x3fffffff;
-                  const int M = m < nx - cj + 1 ? m : nx - cj + 1;
-                  const int k = inl ? S.template claim_run_cap<true>(c, pod, M) : S.template claim_run_cap<false>(c, pod, M);
+                  int pos = jj, k;
+                  int64_t credit;  // the run pods' algorithmic bytes
+                  const int64_t ab0 = S.algbytes;
+                  if constexpr (KS_RUN_CROSS) {
+                    // The run stays on its claim across re-sorts.  Its capacity for this pod is taken once; each
+                    // segment runs to the pod that lifts the claim's count past the next position's, where the
+                    // next add() would re-sort: the descent's count is stored and sort_claims runs as it would
+                    // there.  The run goes on at the claim's new position p' while every position before p' fails
+                    // the quick test (an upper bound, so a certain reject; those claims did not change in this
+                    // step).  One that passes stops it: the array is sorted and the next pod takes its own step.
+                    const int cap = inl ? S.template claim_run_cap<true>(c, pod, m) : S.template claim_run_cap<false>(c, pod, m);
+                    int left = m < cap ? m : cap, K = uni(S.s_okey[jj]);
+                    // a segment's pods are credited with the first pod's span, the re-sort's regather and the
+                    // quick-scan chunks swapped for the segment's own
+                    const int64_t qbytes = 8 * R + 4;
+                    const int64_t span0 = ab0 - abPop - sortB - (int64_t)min((jj / kWave + 1) * kWave, nclaims) * qbytes;
+                    int64_t per = ab0 - abPop;
+                    k = 0;
+                    credit = 0;
+                    while (U(left > 0)) {
+                      if (!srt) {
+                        PH_BEGIN(tx);
+                        exact += S.sort_claims(nclaims);
+                        slow++;
+                        srt = true;
+#ifdef KS_PHASE_STATS
+                        {  // the re-sort's cycles go to the sort phase, not to the commit phase around it
+                          const uint64_t dt = __builtin_amdgcn_s_memtime() - tx;
+                          cyc[2] += dt;
+                          cyc[5] -= dt;
+                        }
+#endif
+                        const int64_t sb = S.algbytes - ab0;
+                        S.algbytes = ab0;
+                        int fq = -1, np = -1;  // the first position passing the quick test; the claim's position
+                        for (int base = 0; base < nclaims; base += kWave) {
+                          const int j = base + lane();
+                          const uint64_t mq = wballot(j < nclaims && S.claim_quick(j, s, sflags, toltpl, pod));
+                          const uint64_t mc = wballot(j < nclaims && S.s_order[j] == c);
+                          if (fq < 0 && mq) fq = base + ctz64(mq);
+                          if (mc) {
+                            np = base + ctz64(mc);
+                            break;
+                          }
+                        }
+                        np = UI(np);
+                        if (np < 0) {  // unreachable: s_order is a permutation of the claims
+                          err = KE_STACK;
+                          qlen = 0;
+                          break;
+                        }
+                        pos = np;
+                        fq = UI(fq);
+                        if (fq >= 0 && fq < pos) {
+                          crossStops++;
+                          stopC = c;
+                          pendSortB = sb;  // the next pod's step: it meets the array sorted
+                          break;
+                        }
+                        cross++;
+                        sorts++;  // (the add() this pod would have entered)
+                        per = span0 + sb + (int64_t)min((pos / kWave + 1) * kWave, nclaims) * qbytes;
+                      }
+                      const int nx = pos + 1 < nclaims ? uni(S.s_okey[pos + 1]) : 0x3fffffff;
+                      int seg = nx - K + 1;
+                      seg = seg < left ? seg : left;
+                      if (seg <= 0) break;  // unreachable: the array is sorted here, so K <= nx
+                      K += seg;
+                      left -= seg;
+                      k += seg;
+                      credit += (int64_t)seg * per;
+                      srt = K <= nx;
+                      S.s_okey[pos] = K;  // wave-wide store of a uniform value
+                      wsync();
+                    }
+                  } else {
+                    const int cj = uni(S.s_okey[jj]);
+                    const int nx = jj + 1 < nclaims ? uni(S.s_okey[jj + 1]) : 0x3fffffff;
+                    const int M = m < nx - cj + 1 ? m : nx - cj + 1;
+                    k = inl ? S.template claim_run_cap<true>(c, pod, M) : S.template claim_run_cap<false>(c, pod, M);
+                    credit = (int64_t)k * (ab0 - abPop);  // each pod scanned as the first one did
+                  }
                   if (k > 0) {
                     int64_t podk[RM];
 #pragma unroll
                     for (int r = 0; r < RM; r++) podk[r] = (int64_t)k * pod[r];
-                    const int64_t ab0 = S.algbytes;
                     int kcnt = 0;
                     if (inl) (void)S.template claim_full<true>(c, s, sflags, podk, req, nthr, kcnt);
                     else (void)S.template claim_full<false>(c, s, sflags, podk, req, nthr, kcnt);
-                    srt = inl ? S.template commit_bulk<true>(c, jj, nclaims, k, podk, req, nthr, kcnt)
-                              : S.template commit_bulk<false>(c, jj, nclaims, k, podk, req, nthr, kcnt);
-                    S.algbytes = ab0 + (int64_t)k * (ab0 - abPop);  // each pod scanned as the first one did
+                    // (KS_RUN_CROSS: the segments stored the count; the headroom at the final position is the
+                    // regathered max - requests of the first pod's commit, less the run's requests)
+                    const int kk = KS_RUN_CROSS ? 0 : k;
+                    srt = inl ? S.template commit_bulk<true>(c, pos, nclaims, kk, podk, req, nthr, kcnt)
+                              : S.template commit_bulk<false>(c, pos, nclaims, kk, podk, req, nthr, kcnt);
+                    S.algbytes = ab0 + credit;
                     if (wi + k <= wn) {  // the run's pods are the window's next lanes
                       const int src = wi + lane() < kWave ? wi + lane() : kWave - 1;
                       S.log_batch(k, __shfl(w.p, src), c, nlog);
@@ -1008,6 +1103,9 @@
     W.counters[CT_RUNS] = runs;
     W.counters[CT_RUN_PODS] = runPods;
     W.counters[CT_SORT_EXACT] = exact;
+    W.counters[CT_RUN_CROSS] = cross;
+    W.counters[CT_RUN_CROSS_STOPS] = crossStops;
+    W.counters[CT_RUN_CROSS_LOST] = crossLost;
 #ifdef KS_PHASE_STATS
     for (int i = 0; i < 7; i++) W.counters[CT_CYC_POP + i] = (int64_t)cyc[i];
     W.counters[CT_CYC_TOTAL] = (int64_t)(__builtin_amdgcn_s_memtime() - tstart);
