@@ -181,9 +181,11 @@ int ks_cons_inspect(const char* snapshot_json, size_t len, char** out_json);
  * counts follow (topology.go:61-85,190-230; the snapshot's clusterPods lose deleted / removed-node pods and
  * gain bound ones).  Candidates, their costs and order, and the simulations are re-derived; the next
  * ks_cons_run sees the new state.  All or nothing: KS_ERR_ARG for unknown / already-deleted / not-pending
- * pods or unknown nodes, KS_ERR_UNSUPPORTED for clusters with volume limits, pods with host ports, and a
- * topology update that would turn a group into one only a relaxation creates (rebuild with ks_cons_create
- * there). */
+ * pods or unknown nodes.  KS_ERR_UNSUPPORTED (rebuild with ks_cons_create there) only for: deleting or binding a
+ * pod that mounts volumes in a cluster with volume limits (pods without volumes and node removals are applied
+ * there too); binding a pod with host ports (deleting one drops its node's entries); and binding a pod that
+ * counts in a topology domain or inverse group the handle does not hold.  A topology group that only a
+ * relaxation creates after the update becomes a late group in place. */
 int ks_cons_update(ks_cons* c, const char* update_json, size_t len);
 /* Host-only: the snapshot with update_json applied ("{}" for none, an array for a sequence), as ks_cons_inspect plus
  * "nodeRows" {name: {available (device units), pods}} for every active node and "poolRemaining". */
@@ -247,6 +249,40 @@ int ks_cons_decide_clock(ks_cons* c, const void* records, int world, int flags, 
  * "replacement-needed" | "instance-types-not-subset", "sim": null | {allNonPendingScheduled,
  * newNodeClaims, claim0: {nodePoolName, instanceTypeOptions}}}.  Leaves the pass's plan unchanged. */
 int ks_cons_validate(ks_cons* c, const char* command_json, size_t len, const ks_solve_opts* opts, char** json_out);
+/* Drift and Expiration (disruption/drift.go, expiration.go), the two other methods that simulate once per
+ * candidate.  The snapshot's stateNodes may carry "nodeClaimConditions": [{type, status, lastTransitionTime}]
+ * (NodeClaim.Status.Conditions as json.Marshal writes them; Drifted and Expired are read; the "cluster" form takes
+ * them from the NodeClaim paired with the node) and a top-level "featureGates": {"drift": bool} (default true).
+ * The method's candidates are the NewCandidate nodes that pass its ShouldDisrupt (drift.go:56-59: the gate and
+ * Drifted True; expiration.go:61-64: the NodePool's expireAfter is a duration and Expired True) and
+ * filterCandidates (PDBs, do-not-disrupt pods), ordered by the condition's lastTransitionTime (sort.Slice
+ * emulated exactly); consolidation's own ShouldDisrupt does not apply.  If any candidate has no pods the command
+ * is all the empty ones and nothing is launched; otherwise every candidate's single-node simulation runs in a
+ * launch of its own on the handle's current state (after ks_cons_update: the updated one) and one more kernel
+ * picks the first candidate whose simulation schedules every non-pending pod and exports all its NewNodeClaims.
+ * The pass's plan, records and ks_cons_last_routes prefix survive; the method's launch is appended to the routes.
+ * No validation follows (the reference has none for these methods).  World 1 only.  opts->lds_budget > 0 caps the
+ * simulations' LDS plan.  JSON {"method": "drift" | "expiration", "candidates": [names in order], "command":
+ * {"action": "no-op" | "delete" | "replace", "candidates": [names], "replacements": [{nodePoolName,
+ * instanceTypeOptions, requests, requirements}]}, "sims": [{candidate, allNonPendingScheduled, newNodeClaims}],
+ * "plan": {KO, KL, lds}, "kernel_ms"}; "sims" lists the simulations the reference would have run, up to and
+ * including the pick (all of them with KS_CONS_ALL_SIMS in flags).  Requests are canonical Quantity text and the
+ * requirements those after FinalizeScheduling (no hostname), as ks_results_json renders a Solve's NodeClaims.  A
+ * simulation keeps no commit log, so the pods per replacement are not reported, and KS_ERR_UNSUPPORTED is returned
+ * when the requests' text would depend on them (pods naming a resource in different quantity formats, or only
+ * some pods naming it while its sum is zero). */
+#define KS_DISRUPT_EXPIRATION 1
+#define KS_DISRUPT_DRIFT 2
+int ks_cons_disrupt(ks_cons* c, int method, const ks_solve_opts* opts, int flags, char** json_out);
+/* Host-only, no device: {"method", "candidates": [names in the method's order], "empty": [the empty ones],
+ * "transitionTimes": [seconds]} of the snapshot with update_json applied (NULL or "{}": none; an array: a sequence). */
+int ks_cons_inspect_disrupt(const char* snapshot_json, size_t len, const char* update_json, size_t ulen, int method,
+                            char** out_json);
+/* Host-only: the bytes ks_cons_save writes for a handle of this snapshot, and ks_cons_inspect_disrupt of a handle
+ * loaded from such bytes (resaved, optional: that handle saved again; free both with ks_free). */
+int ks_cons_encode_binary(const char* snapshot_json, size_t len, void** buf, size_t* buf_len);
+int ks_cons_inspect_disrupt_binary(const void* buf, size_t len, int method, char** out_json, void** resaved,
+                                   size_t* resaved_len);
 /* Diagnostics: the 24 solve counters of simulation `sim` in the last ks_cons_run of this handle. */
 int ks_cons_sim_counters(ks_cons* c, int sim, int64_t* out24);
 /* The same for up to n counters (27 in this build: + runs of identical pods, pods they placed, exact claim

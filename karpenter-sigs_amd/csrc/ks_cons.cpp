@@ -34,6 +34,7 @@
 #include "../../include/karpenter_amd.h"
 #include "ks_gosort.h"
 #include "ks_archive.h"
+#include "ks_disrupt.h"
 #include "ks_host.h"
 #include "ks_parallel.h"
 #include "ks_runtime.h"
@@ -219,7 +220,16 @@ struct ks_cons {
     Cand k;                // pods and cost filled in by order_candidates
     double remaining = 1;  // lifetimeRemaining (types.go:136-145)
     bool passOk = true;    // ShouldDisrupt for the pass (consolidateAfter is not Never)
+    // Consolidation's other ShouldDisrupt tests (the do-not-consolidate annotation, the pool's policy) fail:
+    // the node is no candidate of a pass or of its validation, only of Drift / Expiration
+    bool consOk = true;
+    // Drift / Expiration ShouldDisrupt (drift.go:56-59, expiration.go:61-64): the NodeClaim's Drifted / Expired
+    // condition is True (and, for Expired, the pool's expireAfter is a duration), and the condition's
+    // lastTransitionTime in seconds (the methods' sort key)
+    bool drifted = false, expired = false;
+    int64_t driftT = 0, expireT = 0;
   };
+  bool driftGate = true;  // options.FeatureGates.Drift (the snapshot's featureGates.drift, default true)
   enum : int32_t { PN_PENDING = -1, PN_DELETING = -2, PN_GONE = -3 };
   std::vector<CandIn> candIn;
   std::vector<std::vector<int>> nodePods;  // [host node] GetNodePods
@@ -324,6 +334,7 @@ struct ks_cons {
   int32_t* rank = nullptr;  // global NewQueue rank of every pod
   // carry_walk: a probe re-run's starting relaxation state per pod (prepare_launch uploads it with the plan)
   const std::vector<int32_t>* carryStart = nullptr;
+  size_t ldsBudget = 0;  // the LDS budget of the plan being built (ks_cons_disrupt's opts->lds_budget; 0: sim_plan's)
   // firstNConsolidationOption's binary search (multinodeconsolidation.go:101-135) as carry_walk resolved it for
   // the last decision: the probes in search order, each the pass's simulation of its prefix or a re-run from
   // the pod objects earlier probes relaxed
@@ -348,6 +359,19 @@ struct ks_cons {
   Walk walk;
   uint64_t passId = 0;  // ks_cons_run calls (a walk is valid for the pass it was computed on)
   Launch LR;            // the re-runs' launch (its buffers are kept between re-runs)
+  // Drift / Expiration (ks_cons_disrupt): the method's launch of one single-candidate simulation per candidate,
+  // and the pick's output buffer (k_disrupt_pick writes it, one copy brings it to hout)
+  Launch LD;
+  int ldMethod = 0;       // the method and update count LD's plan was built for (0: none)
+  int64_t ldUpdates = -1;
+  size_t ldBudget = 0, ldCap = 0;  // its LDS budget; the output buffer's words
+  std::vector<int> ldOrder;        // the method's candidates in order (candIn indices), for ordMethod / ordUpdates
+  int ordMethod = 0;
+  int64_t ordUpdates = -1;
+  int32_t* dout = nullptr;
+  int32_t* hout = nullptr;  // pinned
+  int32_t* dpos = nullptr;  // launch slot per position of the method's order
+  size_t capDout = 0, capDpos = 0;
   // the k_solve launches since the last ks_cons_run began, in order: the pass's (both streams of a split or a
   // two-phase topology plan), then those of the carried-probe re-runs and of validate() (ks_cons_last_routes)
   std::vector<Route> routes;
@@ -365,6 +389,10 @@ struct ks_cons {
     if (pb && pb->device >= 0 && hipGetDevice(&prev) == hipSuccess) (void)hipSetDevice(pb->device);
     free_launch();
     LR.release();
+    LD.release();
+    if (dout) (void)hipFree(dout);
+    if (dpos) (void)hipFree(dpos);
+    if (hout) (void)hipHostFree(hout);
     if (rank) (void)hipFree(rank);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -396,7 +424,7 @@ void order_candidates(ks_cons& c) {
       sum += c.podCost[(size_t)p];
       blocked = blocked || (c.podBlock[(size_t)p] & 1);
     }
-    if (blocked) continue;
+    if (blocked || !ci.consOk) continue;
     cost[i] = sum * ci.remaining;
     (ci.passOk ? pass : valOnly).push_back((int)i);
   }
@@ -465,7 +493,7 @@ void build_cons(ks_cons& c, const Value& rootIn) {
   // cluster-state informers would hold (ks_cluster_state)
   Value root = rootIn;
   if (const Value* cl = rootIn.get("cluster"); cl && !rootIn.get("stateNodes")) {
-    const std::string sn = cluster_state_json(*cl);
+    const std::string sn = cluster_state_json(*cl, true);  // (with the NodeClaims' conditions, for Drift / Expiration)
     root.o = std::make_shared<ksjson::Object>(rootIn.obj());
     (*root.o)["stateNodes"] = ksjson::Parser(sn.data(), sn.size()).parse();
   }
@@ -580,6 +608,8 @@ void build_cons(ks_cons& c, const Value& rootIn) {
       }
   const int64_t nowNs = parse_rfc3339(jstr(&root, "now")) * 1000000000;
   const std::vector<Pdb> pdbs = parse_pdbs(root);
+  if (const Value* fg = root.get("featureGates"); fg && fg->is_obj() && fg->get("drift"))
+    c.driftGate = fg->get("drift")->boolean(true);
 
   // per pod: where it is, its eviction cost and whether it blocks its node (filterCandidates, helpers.go:47-71:
   // a PDB allowing no eviction or a do-not-disrupt pod); bit 1 is the verdict for a pending pod once bound
@@ -637,10 +667,28 @@ void build_cons(ks_cons& c, const Value& rootIn) {
       if (c.nominated.count(name)) continue;  // types.go:110-113
       // ShouldDisrupt: consolidation.go:96-108 for the pass; validation.go:112-118 (no consolidateAfter
       // test) admits the rest for mapCandidates after the wait
-      if (ann && ann->is_obj() && jstr(ann, "karpenter.sh/do-not-consolidate") == "true") continue;
-      if (policyOff.count(lp->second)) continue;
       ks_cons::CandIn ci;
+      ci.consOk = !(ann && ann->is_obj() && jstr(ann, "karpenter.sh/do-not-consolidate") == "true") &&
+                  !policyOff.count(lp->second);
       ci.passOk = !afterNever.count(lp->second);
+      // NodeClaim.Status.Conditions as json.Marshal writes them: Drifted / Expired (GetCondition: first match)
+      if (const Value* cs = nv.get("nodeClaimConditions"); cs && cs->kind == Value::Arr) {
+        bool seenD = false, seenE = false;
+        for (const Value& cv : cs->arr()) {
+          const std::string ty = jstr(&cv, "type");
+          const bool on = jstr(&cv, "status") == "True";
+          const int64_t at = parse_rfc3339(jstr(&cv, "lastTransitionTime"));
+          if (ty == "Drifted" && !seenD) {
+            seenD = true;
+            ci.drifted = on;
+            ci.driftT = at;
+          } else if (ty == "Expired" && !seenE) {
+            seenE = true;
+            ci.expired = on && expire.count(lp->second);
+            ci.expireT = at;
+          }
+        }
+      }
       ks_cons::Cand& k = ci.k;
       k.node = hn->second;
       k.name = name;
@@ -866,9 +914,10 @@ std::vector<int32_t> sim_topology(const ks_cons& c, const ks_cons::Sim& sm, cons
 // A pass's LDS plan: a small budget per simulation so several simulations share a CU.  A pass with topology is
 // bound by its longest simulation (a multi-node prefix), not by throughput: its simulations get room for the
 // instance-type tables in LDS (TL) at the price of fewer resident per CU.  maxP: the longest simulation's pods.
-Plan sim_plan(const KsDims& d, int maxP) {
+Plan sim_plan(const KsDims& d, int maxP, size_t budget = 0) {
   KsDims dd = d;
   dd.Kcap = std::max(1, std::min(maxP, 16384));
+  if (budget) return make_plan(dd, std::min<size_t>(budget, 160 * 1024 - 256), true);  // (a caller's lds_budget)
   Plan pl = make_plan(dd, d.G ? 64 * 1024 : 40 * 1024, true);
   if (pl.lds > 80 * 1024 || pl.KO < 1) pl = make_plan(dd, 160 * 1024 - 256, true);
   return pl;
@@ -1243,7 +1292,7 @@ void prepare_launch(ks_cons& c, int rank, int world) {
   if (ai.total) HIPCHK(hipMemcpy(ibase, stage.data(), ai.total, hipMemcpyHostToDevice));
   if (ns) HIPCHK(hipMemcpy(c.L.lworks, works.data(), sizeof(KsWork) * ns, hipMemcpyHostToDevice));
   c.L.lhost = works;
-  c.L.lplan = sim_plan(d, maxP);
+  c.L.lplan = sim_plan(d, maxP, c.ldsBudget);
   if (c.L.lplan.lds > 160 * 1024 || c.L.lplan.KO < 1) throw KsError(KS_ERR_CAPACITY, "simulation state does not fit in LDS");
   // Simulations of at least 256 pods (the multi-node prefixes lead the plan) get 4-wave workgroups in one
   // mixed launch when the plan is chain-bound: its pods number at most kMwChainRatio times its longest
@@ -1647,7 +1696,10 @@ namespace {
 
 // The queue sort + simulation kernel over this rank's simulations; records to host or device memory.
 // Returns the HIP-event time of both launches on the stream they ran on.
-double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice) {
+// tail: enqueued on the stream behind the simulations in place of the record copies (the records and
+// workspaces stay on the device for it), before the one synchronisation.
+double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice,
+                const std::function<void(hipStream_t)>* tail = nullptr) {
   PhaseTimer pt("run_sims");
   RouteScope routeScope(&c.routes);
   prepare_launch(c, rank, world);
@@ -1703,7 +1755,9 @@ double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice) {
   pt.mark("launches enqueued");
   // the records follow on the same stream; one synchronisation covers both
   const size_t bytes = 4 * (size_t)c.recWords * ns, all = 4 * (size_t)c.recWords * c.per_rank(world);
-  if (onDevice) {
+  if (tail) {
+    (*tail)(pb.stream);
+  } else if (onDevice) {
     if (all > bytes) HIPCHK(hipMemsetAsync((char*)records + bytes, 0, all - bytes, pb.stream));
     if (bytes) HIPCHK(hipMemcpyAsync(records, c.L.lrec, bytes, hipMemcpyDeviceToDevice, pb.stream));
   } else if (!records && world == 1 && !std::getenv("KS_CONS_FULL_RECORDS")) {  // records stay in the handle: headers only
@@ -1727,8 +1781,8 @@ double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice) {
   pt.mark("record copies enqueued");
   HIPCHK(hipStreamSynchronize(pb.stream));
   pt.mark("synchronized");
-  c.L.hdrOnly = !onDevice && !records && world == 1 && !std::getenv("KS_CONS_FULL_RECORDS");
-  c.L.keptFull = !onDevice && !records && world == 1 && !c.L.hdrOnly;
+  c.L.hdrOnly = !tail && !onDevice && !records && world == 1 && !std::getenv("KS_CONS_FULL_RECORDS");
+  c.L.keptFull = !tail && !onDevice && !records && world == 1 && !c.L.hdrOnly;
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
   if (!onDevice && records) {  // (records == NULL: they stay in the handle's pinned buffer, host_records)
@@ -2535,6 +2589,298 @@ std::string inspect_json(const ks_cons& c, bool nodes) {
   return o;
 }
 
+// ---- Drift and Expiration (drift.go, expiration.go) ----------------------------------------------------
+// The method's candidates in its order: the candIn entries that pass the method's ShouldDisrupt (drift.go:56-59:
+// the feature gate and Drifted; expiration.go:61-64: an expireAfter duration and Expired) and filterCandidates
+// (helpers.go:47-71, the pass's PDB / do-not-disrupt verdict), then sort.Slice by the condition's
+// lastTransitionTime with Before (drift.go:67-70, expiration.go:72-75), Go's pdqsort emulated exactly over the
+// times' dense ranks.  Consolidation's own ShouldDisrupt (passOk, consOk) does not apply.  Returns candIn indices.
+const char* method_name(int method) { return method == KS_DISRUPT_DRIFT ? "drift" : "expiration"; }
+
+std::vector<int> method_candidates(const ks_cons& c, int method) {
+  if (method != KS_DISRUPT_DRIFT && method != KS_DISRUPT_EXPIRATION) throw KsError(KS_ERR_ARG, "unknown disruption method");
+  std::vector<int> in;
+  std::vector<int64_t> at;
+  for (size_t i = 0; i < c.candIn.size(); i++) {
+    const ks_cons::CandIn& ci = c.candIn[i];
+    if (c.nodeGone[(size_t)ci.k.node]) continue;
+    if (method == KS_DISRUPT_DRIFT ? !(c.driftGate && ci.drifted) : !ci.expired) continue;
+    bool blocked = false;
+    for (int p : c.nodePods[(size_t)ci.k.node]) blocked = blocked || (c.podBlock[(size_t)p] & 1);
+    if (blocked) continue;
+    in.push_back((int)i);
+    at.push_back(method == KS_DISRUPT_DRIFT ? ci.driftT : ci.expireT);
+  }
+  const int n = (int)in.size();
+  std::vector<int64_t> vals(at);
+  std::sort(vals.begin(), vals.end());
+  std::vector<int32_t> key((size_t)n), idx((size_t)n);
+  for (int i = 0; i < n; i++) {
+    key[(size_t)i] = (int32_t)(std::lower_bound(vals.begin(), vals.end(), at[(size_t)i]) - vals.begin());
+    idx[(size_t)i] = i;
+  }
+  GoSortExact g{GoSort{key.data(), idx.data()}};
+  g.run(n);
+  std::vector<int> out((size_t)n);
+  for (int i = 0; i < n; i++) out[(size_t)i] = in[(size_t)idx[(size_t)i]];
+  return out;
+}
+
+void put_names(std::string& o, const ks_cons& c, const std::vector<int>& order, bool emptyOnly) {
+  o += "[";
+  bool first = true;
+  for (int ii : order) {
+    const ks_cons::CandIn& ci = c.candIn[(size_t)ii];
+    if (emptyOnly && !c.nodePods[(size_t)ci.k.node].empty()) continue;
+    if (!first) o += ",";
+    first = false;
+    ksjson::quote(o, ci.k.name);
+  }
+  o += "]";
+}
+
+// Host-only description: the ordered candidates, the empty ones and the sort keys.
+std::string inspect_disrupt_json(const ks_cons& c, int method) {
+  const std::vector<int> order = method_candidates(c, method);
+  std::string o = std::string("{\"method\":\"") + method_name(method) + "\",\"candidates\":";
+  put_names(o, c, order, false);
+  o += ",\"empty\":";
+  put_names(o, c, order, true);
+  o += ",\"transitionTimes\":[";
+  for (size_t i = 0; i < order.size(); i++) {
+    const ks_cons::CandIn& ci = c.candIn[(size_t)order[i]];
+    o += (i ? "," : "") + std::to_string(method == KS_DISRUPT_DRIFT ? ci.driftT : ci.expireT);
+  }
+  return o + "]}";
+}
+
+// A NodeClaim's requests as canonical Quantity text.  The Merge that builds them (resources.go:53-63) adopts an
+// addend's format while the sum is zero, so the text depends on which pods the claim holds and in which order,
+// and a simulation keeps no commit log (k_solve<SIM> counts its commits only).  The text is still determined
+// when every pod of the simulation that names a resource writes it in one format and agrees with the others on
+// naming it; a simulation where that does not hold is refused (KS_ERR_UNSUPPORTED) instead of guessed.
+std::string claim_requests_json(const Host& h, const std::vector<int>& simPods, int tpl, const int64_t* creq) {
+  const KsDims& d = h.dims;
+  if (d.negReq) throw KsError(KS_ERR_UNSUPPORTED, "disrupt: negative requests (the requests' text needs the commit order)");
+  QList req;
+  for (int r = 0; r < d.R; r++) {
+    const bool tplHas = (h.tab.tpl_rmask[(size_t)tpl] >> r) & 1u;
+    int with = 0;
+    std::set<int> fmts;
+    for (int p : simPods)
+      if ((h.tab.pod_rmask[(size_t)p] >> r) & 1u) {
+        with++;
+        fmts.insert((int)h.tab.pod_rfmt[(size_t)p * d.R + r]);
+      }
+    const bool present = tplHas || creq[r] != 0 || (with > 0 && with == (int)simPods.size());
+    if (!present) {
+      if (with > 0)
+        throw KsError(KS_ERR_UNSUPPORTED, "disrupt: only some pods name resource " + h.resNames[(size_t)r] +
+                                              " (the requests' keys need the pods per NodeClaim)");
+      continue;
+    }
+    int fmt = (int)h.tab.tpl_rfmt[(size_t)tpl * d.R + r];
+    if (h.tab.tpl_daemon[(size_t)tpl * d.R + r] == 0 && !fmts.empty()) {
+      if (fmts.size() > 1)
+        throw KsError(KS_ERR_UNSUPPORTED, "disrupt: pods write resource " + h.resNames[(size_t)r] +
+                                              " in more than one quantity format");
+      fmt = *fmts.begin();
+    }
+    Qty q = h.fromDev(r, creq[r]);
+    q.f = (QFmt)fmt;
+    req.emplace_hint(req.end(), h.resNames[(size_t)r], q);
+  }
+  std::string o = "{";
+  bool first = true;
+  for (auto& kv : req) {
+    if (!first) o += ",";
+    first = false;
+    ksjson::quote(o, kv.first);
+    o += ":";
+    ksjson::quote(o, qty_str(kv.second));
+  }
+  return o + "}";
+}
+
+// Drift / Expiration ComputeCommand (drift.go:77-118, expiration.go:83-120) on the handle's current state.
+std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool allSims) {
+  PhaseTimer pt("ks_cons_disrupt");
+  const Host& h = c.pb->host;
+  const KsDims& d = h.dims;
+  // (the order and the plan are kept while the method and the state they were derived from stay the same)
+  if (!(c.ordMethod == method && c.ordUpdates == c.updates)) {
+    c.ordMethod = 0;
+    c.ldOrder = method_candidates(c, method);
+    c.ordMethod = method;
+    c.ordUpdates = c.updates;
+  }
+  const std::vector<int>& order = c.ldOrder;
+  const int n = (int)order.size();
+  std::string o = std::string("{\"method\":\"") + method_name(method) + "\",\"candidates\":";
+  put_names(o, c, order, false);
+  bool anyEmpty = false;
+  for (int ii : order) anyEmpty = anyEmpty || c.nodePods[(size_t)c.candIn[(size_t)ii].k.node].empty();
+  if (n == 0 || anyEmpty) {
+    // no candidate, or every empty one at once: no simulation (drift.go:86-92, expiration.go:91-97)
+    o += std::string(",\"command\":{\"action\":\"") + (anyEmpty ? "delete" : "no-op") + "\",\"candidates\":";
+    if (anyEmpty) put_names(o, c, order, true);
+    else o += "[]";
+    return o + ",\"replacements\":[]},\"sims\":[],\"kernel_ms\":0}";
+  }
+  // the method's plan: one single-candidate simulation per candidate, in the method's order, in a launch of its
+  // own (LD); the pass's candidates, simulations and launch come back afterwards
+  const size_t budget = opts && opts->lds_budget > 0 ? (size_t)opts->lds_budget : 0;
+  const int stride = disrupt_claim_words(d.R, d.TW, d.RSW);
+  const bool fresh = !(c.ldMethod == method && c.ldUpdates == c.updates && c.ldBudget == budget && c.LD.lrank == 0 &&
+                       c.LD.lworld == 1 && (int)c.LD.lsims.size() == n);
+  std::vector<ks_cons::Cand> mc;
+  std::vector<ks_cons::Sim> ms;
+  if (fresh) {  // (a kept plan is launched as it is: nothing reads the candidates or the simulations again)
+    mc.resize((size_t)n);
+    ms.resize((size_t)n);
+    int maxP = 1;
+    for (int i = 0; i < n; i++) {
+      const ks_cons::CandIn& ci = c.candIn[(size_t)order[(size_t)i]];
+      mc[(size_t)i] = ci.k;
+      mc[(size_t)i].pods = c.nodePods[(size_t)ci.k.node];
+      ms[(size_t)i].cands.assign(1, i);
+      maxP = std::max(maxP, (int)(c.pending.size() + c.deleting.size() + mc[(size_t)i].pods.size()));
+    }
+    // a simulation of P pods creates at most P claims
+    c.ldCap = (size_t)DH_WORDS + (size_t)n + (size_t)maxP * (size_t)stride;
+    c.ldMethod = 0;  // (not a valid plan until the launch below is built)
+  }
+  const size_t cap = c.ldCap;
+  if (cap > 0x7fffffffu) throw KsError(KS_ERR_CAPACITY, "disrupt: output buffer too large");
+  int nPass = n, multiHi = 0;
+  auto swapPlan = [&]() {
+    if (!fresh) return;
+    mc.swap(c.cands);
+    ms.swap(c.sims);
+    std::swap(nPass, c.nPass);
+    std::swap(multiHi, c.multiHi);
+  };
+  swapPlan();
+  std::swap(c.L, c.LD);
+  if (fresh) c.L.invalidate();
+  c.ldsBudget = budget;
+  auto restore = [&]() {
+    c.ldsBudget = 0;
+    std::swap(c.L, c.LD);
+    swapPlan();
+  };
+  double ms_ = 0;
+  Plan plan{};
+  try {
+    if (cap * 4 > c.capDout || !c.dout) {
+      if (c.dout) HIPCHK(hipFree(c.dout));
+      if (c.hout) HIPCHK(hipHostFree(c.hout));
+      c.dout = c.hout = nullptr;
+      c.capDout = 0;
+      HIPCHK(hipMalloc((void**)&c.dout, cap * 4));
+      HIPCHK(hipHostMalloc((void**)&c.hout, cap * 4, hipHostMallocDefault));
+      c.capDout = cap * 4;
+    }
+    if ((size_t)n * 4 > c.capDpos || !c.dpos) {
+      if (c.dpos) HIPCHK(hipFree(c.dpos));
+      c.dpos = nullptr;
+      c.capDpos = 0;
+      HIPCHK(hipMalloc((void**)&c.dpos, (size_t)n * 4));
+      c.capDpos = (size_t)n * 4;
+    }
+    if (fresh) {  // position i of the method's order runs in launch slot i
+      std::vector<int32_t> slot((size_t)n);
+      for (int i = 0; i < n; i++) slot[(size_t)i] = i;
+      HIPCHK(hipMemcpy(c.dpos, slot.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    const std::function<void(hipStream_t)> tail = [&](hipStream_t st) {
+      HIPCHK(disrupt_pick(c.L.lrec, c.recWords, c.L.lworks, c.dpos, n, d.R, d.TW, d.RSW, c.dout, (int)cap, st));
+      // one copy: the header, the positions and the picked simulation's claims (at most cap words)
+      HIPCHK(hipMemcpyAsync(c.hout, c.dout, cap * 4, hipMemcpyDeviceToHost, st));
+    };
+    ms_ = run_sims(c, 0, 1, nullptr, false, &tail);
+    c.ldMethod = method;
+    c.ldUpdates = c.updates;
+    c.ldBudget = budget;
+    plan = c.L.lplan;
+    if ((int)c.L.lsims.size() != n) throw KsError(KS_ERR_INTERNAL, "disrupt: the method's launch lost simulations");
+  } catch (...) {
+    c.ldMethod = 0;
+    restore();
+    throw;
+  }
+  restore();
+  pt.mark("simulations + pick");
+  const int32_t* out = c.hout;
+  const int pick = out[DH_PICK], errp = out[DH_ERRPOS];
+  if (pick < -1 || pick >= n || errp < -1 || errp >= n) throw KsError(KS_ERR_INTERNAL, "disrupt: pick out of range");
+  if (errp >= 0 && (pick < 0 || errp <= pick))  // (as check_records does for a pass)
+    throw KsError(out[DH_ERR] == KE_CLAIM_CAP ? KS_ERR_CAPACITY : KS_ERR_INTERNAL,
+                  "disrupt simulation " + std::to_string(errp) + " reported kernel error " + std::to_string(out[DH_ERR]));
+  const int nclaims = out[DH_NCLAIMS];
+  if (out[DH_NEED] > (int)cap || out[DH_EXPORTED] != nclaims || out[DH_BAD])
+    throw KsError(KS_ERR_INTERNAL, "disrupt: pick output incomplete (needs " + std::to_string(out[DH_NEED]) + " of " +
+                                       std::to_string(cap) + " words, exported " + std::to_string(out[DH_EXPORTED]) + " of " +
+                                       std::to_string(nclaims) + " NodeClaims, bad order " + std::to_string(out[DH_BAD]) + ")");
+  const int32_t* posw = out + DH_WORDS;
+  if (pick >= 0 && ((posw[pick] >> 8) != nclaims || !(posw[pick] & RB_ALL_SCHEDULED)))
+    throw KsError(KS_ERR_INTERNAL, "disrupt: the picked simulation's record and workspace disagree");
+  // the command
+  o += ",\"command\":{\"action\":\"";
+  o += pick < 0 ? "no-op" : nclaims > 0 ? "replace" : "delete";
+  o += "\",\"candidates\":[";
+  if (pick >= 0) ksjson::quote(o, c.candIn[(size_t)order[(size_t)pick]].k.name);
+  o += "],\"replacements\":[";
+  if (pick >= 0 && nclaims > 0) {
+    const ks_cons::CandIn& ci = c.candIn[(size_t)order[(size_t)pick]];
+    std::vector<int> simPods = c.pending;
+    simPods.insert(simPods.end(), c.nodePods[(size_t)ci.k.node].begin(), c.nodePods[(size_t)ci.k.node].end());
+    simPods.insert(simPods.end(), c.deleting.begin(), c.deleting.end());
+    const int32_t* cl = posw + n;
+    for (int k = 0; k < nclaims; k++, cl += stride) {
+      const int tpl = cl[0];
+      if (tpl < 0 || tpl >= d.NTPL) throw KsError(KS_ERR_INTERNAL, "disrupt: NodeClaim template out of range");
+      const std::vector<int> its = bits_to_its(h, tpl, cl + 3);
+      int nopt = 0;
+      for (int w = 0; w < d.TW; w++) nopt += __builtin_popcount((uint32_t)cl[3 + w]);
+      if (nopt != cl[2] || nopt == 0 || (int)its.size() != nopt)
+        throw KsError(KS_ERR_INTERNAL, "disrupt: NodeClaim option count");
+      std::vector<int64_t> creq((size_t)d.R);
+      memcpy(creq.data(), cl + 3 + d.TW, 8 * (size_t)d.R);
+      const uint32_t* rs = (const uint32_t*)(cl + 3 + d.TW + 2 * d.R);
+      if (k) o += ",";
+      o += "{\"nodePoolName\":";
+      ksjson::quote(o, h.tpls[(size_t)tpl].pool);
+      o += ",\"instanceTypeOptions\":" + names_json(h, its);
+      o += ",\"requests\":" + claim_requests_json(h, simPods, tpl, creq.data());
+      o += ",\"requirements\":[";
+      const uint64_t pr = rs_present(rs);
+      bool first = true;
+      for (int kk = 0; kk < d.NK; kk++) {  // FinalizeScheduling dropped the hostname requirement
+        if (!bit(pr, kk) || kk == h.hostKey) continue;
+        if (!first) o += ",";
+        first = false;
+        ksjson::quote(o, h.reqString(rs, kk, true, c.hostnameSeed + cl[1]));
+      }
+      o += "]}";
+    }
+  }
+  o += "]},\"sims\":[";
+  // the simulations the reference runs: up to and including the pick (all of them with KS_CONS_ALL_SIMS)
+  const int last = allSims || pick < 0 ? n - 1 : pick;
+  for (int i = 0; i <= last; i++) {
+    if (i) o += ",";
+    o += "{\"candidate\":";
+    ksjson::quote(o, c.candIn[(size_t)order[(size_t)i]].k.name);
+    o += std::string(",\"allNonPendingScheduled\":") + ((posw[i] & RB_ALL_SCHEDULED) ? "true" : "false") +
+         ",\"newNodeClaims\":" + std::to_string(posw[i] >> 8) + "}";
+  }
+  char buf[160];
+  snprintf(buf, sizeof buf, "],\"plan\":{\"KO\":%d,\"KL\":%d,\"lds\":%llu},\"kernel_ms\":%.6f}", plan.KO, plan.KL,
+           (unsigned long long)plan.lds, ms_);
+  return o + buf;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2587,16 +2933,18 @@ extern "C++" {
 namespace ks {
 template <class A> void io(A& a, ks_cons::Cand& x) { io_all(a, x.node, x.name, x.pool, x.ct, x.zone, x.it, x.cost, x.pods); }
 template <class A> void io(A& a, ks_cons::Sim& x) { io_all(a, x.cands, x.multi); }
-template <class A> void io(A& a, ks_cons::CandIn& x) { io_all(a, x.k, x.remaining, x.passOk); }
+template <class A> void io(A& a, ks_cons::CandIn& x) { io_all(a, x.k, x.remaining, x.passOk, x.consOk, x.drifted, x.expired, x.driftT, x.expireT);
+}
 }  // namespace ks
 namespace {
 // the format version, with the embedded problem's (KSPROBnn): 05 = round 6 (KSPROB05); 04 = round 5's final
 // layout (KSPROB04);
 // 03 = round 5's first (KSPROB03); 02 = round 4; 01 = round 3.  Another version is refused (snapshot_check_header).
-constexpr char kConsMagic[8] = {'K', 'S', 'C', 'O', 'N', 'S', '0', '5'};
+// 06 adds the Drift / Expiration inputs (CandIn's conditions, the feature gate) to 05's layout.
+constexpr char kConsMagic[8] = {'K', 'S', 'C', 'O', 'N', 'S', '0', '6'};
 template <class A> void cons_io(A& a, ks_cons& c) {
   io_all(a, c.cands, c.nPass, c.sims, c.multiHi, c.pending, c.deleting, c.nominated, c.hostnameSeed, c.recWords,
-         c.candIn, c.nodePods, c.podNode, c.podBlock, c.podCost, c.nodeGone, c.updates);
+         c.candIn, c.nodePods, c.podNode, c.podBlock, c.podCost, c.nodeGone, c.updates, c.driftGate);
 }
 // The loaded plan's indices must lie inside the loaded model (host_check covers the model itself).
 void cons_check(const ks_cons& c) {
@@ -2631,23 +2979,18 @@ void cons_check(const ks_cons& c) {
 }  // namespace
 }  // extern "C++"
 
-int ks_cons_save(const ks_cons* c, void** buf, size_t* len) {
-  API_TRY
-  if (!c || !buf || !len) throw KsError(KS_ERR_ARG, "null argument");
+extern "C++" {
+namespace {
+void cons_save(const ks_cons& c, void** buf, size_t* len) {
   ArOut a;
   snapshot_header(a, kConsMagic);
-  host_save(a, c->pb->host);
-  cons_io(a, const_cast<ks_cons&>(*c));
+  host_save(a, c.pb->host);
+  cons_io(a, const_cast<ks_cons&>(c));
   *buf = snapshot_bytes(a.buf);
   *len = a.buf.size();
-  return KS_OK;
-  API_CATCH
 }
-
-int ks_cons_create_binary(const void* buf, size_t len, ks_cons** out) {
-  API_TRY
-  if (!buf || !out) throw KsError(KS_ERR_ARG, "null argument");
-  PhaseTimer pt("ks_cons_create_binary");
+// the host half of ks_cons_create_binary
+std::unique_ptr<ks_cons> cons_load(const void* buf, size_t len) {
   std::unique_ptr<ks_cons> c(new ks_cons());
   c->pb.reset(new ks_problem());
   try {
@@ -2660,6 +3003,47 @@ int ks_cons_create_binary(const void* buf, size_t len, ks_cons** out) {
   } catch (const ArchiveError& e) {
     throw KsError(KS_ERR_PARSE, e.what());
   }
+  return c;
+}
+}  // namespace
+}  // extern "C++"
+
+int ks_cons_save(const ks_cons* c, void** buf, size_t* len) {
+  API_TRY
+  if (!c || !buf || !len) throw KsError(KS_ERR_ARG, "null argument");
+  cons_save(*c, buf, len);
+  return KS_OK;
+  API_CATCH
+}
+
+// Host-only (no device): the binary snapshot ks_cons_save would write for a handle of this snapshot.
+int ks_cons_encode_binary(const char* json, size_t len, void** buf, size_t* blen) {
+  API_TRY
+  if (!json || !buf || !blen) throw KsError(KS_ERR_ARG, "null argument");
+  ksjson::Value root = ksjson::Parser(json, len ? len : strlen(json)).parse();
+  ks_cons c;
+  build_cons(c, root);
+  cons_save(c, buf, blen);
+  return KS_OK;
+  API_CATCH
+}
+
+// Host-only: ks_cons_inspect_disrupt of a binary snapshot's handle; resaved (optional): the loaded handle saved again.
+int ks_cons_inspect_disrupt_binary(const void* buf, size_t len, int method, char** out, void** resaved, size_t* rlen) {
+  API_TRY
+  if (!buf || !out || (resaved && !rlen)) throw KsError(KS_ERR_ARG, "null argument");
+  std::unique_ptr<ks_cons> c = cons_load(buf, len);
+  if (resaved) cons_save(*c, resaved, rlen);
+  *out = strdup(inspect_disrupt_json(*c, method).c_str());
+  return KS_OK;
+  API_CATCH
+}
+
+int ks_cons_create_binary(const void* buf, size_t len, ks_cons** out) {
+  API_TRY
+  if (!buf || !out) throw KsError(KS_ERR_ARG, "null argument");
+  PhaseTimer pt("ks_cons_create_binary");
+  std::unique_ptr<ks_cons> c = cons_load(buf, len);
   pt.mark("load");
   cons_device_init(c.get(), pt);
   *out = c.release();
@@ -2760,6 +3144,38 @@ int ks_cons_validate(ks_cons* c, const char* command_json, size_t len, const ks_
   ksjson::Value cmd = ksjson::Parser(command_json, len ? len : strlen(command_json)).parse();
   if (!cmd.is_obj()) throw KsError(KS_ERR_PARSE, "command is not an object");
   *json_out = strdup(validate_json(*c, cmd).c_str());
+  return KS_OK;
+  API_CATCH
+}
+
+int ks_cons_disrupt(ks_cons* c, int method, const ks_solve_opts* opts, int flags, char** json_out) {
+  API_TRY
+  if (!c || !json_out) throw KsError(KS_ERR_ARG, "null argument");
+  c->check_usable();
+  DeviceGuard guard(c->pb->device, opts);
+  *json_out = strdup(disrupt_json(*c, method, opts, (flags & KS_CONS_ALL_SIMS) != 0).c_str());
+  return KS_OK;
+  API_CATCH
+}
+
+// Host-only: the method's candidates in order and the empty ones, for the snapshot with update_json applied
+// (NULL or "{}": as it is; an array: a sequence).
+int ks_cons_inspect_disrupt(const char* json, size_t len, const char* update_json, size_t ulen, int method, char** out) {
+  API_TRY
+  if (!json || !out) throw KsError(KS_ERR_ARG, "null argument");
+  ksjson::Value root = ksjson::Parser(json, len ? len : strlen(json)).parse();
+  ks_cons c;
+  build_cons(c, root);
+  root = ksjson::Value();
+  if (update_json) {
+    const ksjson::Value delta = ksjson::Parser(update_json, ulen ? ulen : strlen(update_json)).parse();
+    if (delta.kind == ksjson::Value::Arr) {
+      for (const ksjson::Value& u : delta.arr()) apply_update(c, u, false);
+    } else if (!(delta.is_obj() && delta.obj().empty())) {
+      apply_update(c, delta, false);
+    }
+  }
+  *out = strdup(inspect_disrupt_json(c, method).c_str());
   return KS_OK;
   API_CATCH
 }

@@ -74,7 +74,9 @@ struct PodH {
 };
 PodH parse_pod(const ksjson::Value& v);
 // Cluster-state accounting (ks_state.cpp): StateNode accessor values from {nodeClaims, nodes, pods}
-std::string cluster_state_json(const ksjson::Value& cluster);
+// withConditions (internal: the consolidation handle's build): each node also carries its NodeClaim's
+// status.conditions as "nodeClaimConditions"; ks_cluster_state's public output never does.
+std::string cluster_state_json(const ksjson::Value& cluster, bool withConditions = false);
 
 struct PodState {  // one point of the relaxation chain
   std::vector<uint32_t> rsAll, rsStrict;

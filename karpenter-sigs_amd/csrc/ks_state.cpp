@@ -169,7 +169,7 @@ void put_qlist(std::string& o, const QList& q) {
 
 }  // namespace
 
-std::string cluster_state_json(const Value& root) {
+std::string cluster_state_json(const Value& root, bool withConditions) {
   std::vector<std::string> order;  // providerIDs, canonical order
   std::map<std::string, Entry> byID;
   auto entry = [&](const std::string& id) -> Entry& {
@@ -354,7 +354,13 @@ std::string cluster_state_json(const Value& root) {
             }
           break;
         }
-    o += "},\"pods\":[";
+    o += "}";
+    if (withConditions)
+      if (const Value* cs = path(e.claim, {"status", "conditions"}); cs && cs->kind == Value::Arr) {
+        o += ",\"nodeClaimConditions\":";
+        dump(o, *cs);
+      }
+    o += ",\"pods\":[";
     for (size_t i = 0; i < e.pods.size(); i++) {
       if (i) o += ",";
       dump(o, *e.pods[i]);

@@ -396,6 +396,13 @@ def _cons_lib():
         l.ks_cons_last_reruns.argtypes = [vp]
         l.ks_cons_last_reruns.restype = ctypes.c_int
         l.ks_cons_last_routes.argtypes = [vp, ctypes.POINTER(vp)]
+        l.ks_cons_disrupt.argtypes = [vp, ctypes.c_int, ctypes.POINTER(_Opts), ctypes.c_int, ctypes.POINTER(vp)]
+        l.ks_cons_inspect_disrupt.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                              ctypes.c_int, ctypes.POINTER(vp)]
+        l.ks_cons_encode_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp),
+                                            ctypes.POINTER(ctypes.c_size_t)]
+        l.ks_cons_inspect_disrupt_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp),
+                                                     ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         l._cons_ready = True
     return l
 
@@ -416,6 +423,48 @@ def inspect_consolidation_update(snapshot, update=None):
     out = ctypes.c_void_p()
     _check(_cons_lib().ks_cons_inspect_update(b, len(b), u, len(u), ctypes.byref(out)))
     return json.loads(_take_str(out))
+
+
+DISRUPT_METHODS = {"expiration": 1, "drift": 2}  # KS_DISRUPT_EXPIRATION / KS_DISRUPT_DRIFT
+
+
+def _method(method):
+    return DISRUPT_METHODS[method] if isinstance(method, str) else int(method)
+
+
+def inspect_disruption(snapshot, method, update=None):
+    """Host-only: the candidates of Drift / Expiration ("drift" | "expiration") in the method's order and the
+    empty ones, for the snapshot with a ks_cons_update delta (or a list of them) applied:
+    {"method", "candidates", "empty", "transitionTimes"}."""
+    b = _encode(snapshot)
+    u = None if update is None else _encode(update)
+    out = ctypes.c_void_p()
+    _check(_cons_lib().ks_cons_inspect_disrupt(b, len(b), u, len(u) if u else 0, _method(method), ctypes.byref(out)))
+    return json.loads(_take_str(out))
+
+
+def encode_consolidation_binary(snapshot):
+    """Host-only: the bytes Consolidator(snapshot).save() writes (no device)."""
+    l = _cons_lib()
+    b = _encode(snapshot)
+    buf, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _check(l.ks_cons_encode_binary(b, len(b), ctypes.byref(buf), ctypes.byref(n)))
+    blob = ctypes.string_at(buf, n.value)
+    l.ks_free(buf)
+    return blob
+
+
+def inspect_disruption_binary(blob, method):
+    """Host-only: inspect_disruption of the handle a binary snapshot loads to; returns (doc, that handle's
+    save() bytes)."""
+    l = _cons_lib()
+    blob = bytes(blob)
+    out, buf, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+    _check(l.ks_cons_inspect_disrupt_binary(blob, len(blob), _method(method), ctypes.byref(out), ctypes.byref(buf),
+                                            ctypes.byref(n)))
+    again = ctypes.string_at(buf, n.value)
+    l.ks_free(buf)
+    return json.loads(_take_str(out)), again
 
 
 def shard_slot(sim, world):
@@ -549,6 +598,16 @@ class Consolidator:
         js = ctypes.c_void_p()
         o = _Opts(device, 1, 1, 0, 0)
         _check(_cons_lib().ks_cons_validate(self._h, b, len(b), ctypes.byref(o), ctypes.byref(js)))
+        return json.loads(_take_str(js))
+
+    def disrupt(self, method, all_sims=False, device=-1, lds_budget=0):
+        """Drift / Expiration ComputeCommand ("drift" | "expiration") on the handle's current state
+        (ks_cons_disrupt): {"method", "candidates", "command": {"action", "candidates", "replacements"}, "sims",
+        "plan", "kernel_ms"}.  The pass's plan and records survive the call."""
+        js = ctypes.c_void_p()
+        o = _Opts(device, 1, 1, 0, lds_budget)
+        _check(_cons_lib().ks_cons_disrupt(self._h, _method(method), ctypes.byref(o), 1 if all_sims else 0,
+                                           ctypes.byref(js)))
         return json.loads(_take_str(js))
 
     def sim_counters(self, sim):
