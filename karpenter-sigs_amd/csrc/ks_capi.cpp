@@ -1375,7 +1375,10 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "cycTotal", "cycNodeCommit", "cycFullRs", "cycFullThr", "cycFullMasks", "cycFullApply",
                                 "runs", "runPods", "sortsExact", "fineTopoPop", "fineState", "fineRefill",
                                 "fineWindowTests", "fineWindowBlocks", "fineRecord", "fineNodeCommit", "fineWindowTopo",
-                                "runCross", "runCrossStops", "runCrossLost"};
+                                "runCross", "runCrossStops", "runCrossLost", "sortsClosed", "tplMemoHits",
+                                "cycSortFast", "cycSortExact", "cycSortClosed", "sortsLe12", "sortsLt50",
+                                "cycRunCap", "cycCross", "cycBulk", "cycLog", "cycTplDerive", "cycTplStore",
+                                "cycTplMax"};
   static_assert(sizeof(names) / sizeof(names[0]) == CT_NCOUNTERS, "one name per counter");
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);
   // the launched k_solve instantiation: the last launch's fields, and every launch of this Solve in order

@@ -328,7 +328,25 @@ enum Counter {
   CT_RUN_CROSS = CT_FINE + 8,  // LEAN Solve claim runs: re-sort crossings continued inside a step
   CT_RUN_CROSS_STOPS,          // continuations refused: a position before the claim's new one passed the quick test
   CT_RUN_CROSS_LOST,           // refusals after which the pod landed on the run's claim all the same (a step lost)
-  CT_NCOUNTERS = 38
+  CT_SORT_CLOSED,              // LEAN Solve claim re-sorts done by the single-descent closed form (KS_SORT_CLOSED)
+  CT_TPL_MEMO_HITS,            // LEAN Solve NewNodeClaims that reused the last one's derived state (KS_TPL_MEMO)
+  // diagnostic build: the LEAN Solve's step in sub-phases (cycles unless noted)
+  CT_STEP,                     // [12], the StepSub slots
+  CT_NCOUNTERS = CT_STEP + 12
+};
+enum StepSub {
+  SS_SORT_FAST = 0,  // re-sorts the wave-parallel partialInsertionSort finished (inside CT_CYC_SORT, as the next two)
+  SS_SORT_EXACT,     // re-sorts that ran the exact pdqsort
+  SS_SORT_CLOSED,    // re-sorts done by the closed form
+  SS_SORTS_LE12,     // (count) re-sorts with a descent of n <= 12 claims
+  SS_SORTS_LT50,     // (count) of 12 < n < 50 claims; the rest of sortsWithDescent had n >= 50
+  SS_RUN_CAP,        // claim_run_cap (inside CT_CYC_COMMIT, as the next three)
+  SS_CROSS,          // the crossing loop without its re-sorts
+  SS_BULK,           // the run's claim_full + commit_bulk
+  SS_LOG,            // the run's log entries
+  SS_TPL_DERIVE,     // try_templates: options, thresholds, count (inside CT_CYC_TPL, as the next two)
+  SS_TPL_STORE,      // try_templates: the claim's state stores and their release
+  SS_TPL_MAX,        // try_templates: recompute_max
 };
 // KE_LEAN_EXIT: a LEAN Solve of pods sharing a UID met its first push-back (the host re-runs it non-LEAN)
 enum KernelError { KE_OK = 0, KE_CLAIM_CAP = 1, KE_ITER_CAP = 2, KE_STACK = 3, KE_LEAN_EXIT = 4 };

@@ -49,6 +49,20 @@
 #ifndef KS_RUN_CROSS  // those runs stay on their NodeClaim across the re-sorts inside a step (0: end at each)
 #define KS_RUN_CROSS 1
 #endif
+#ifndef KS_SORT_CLOSED  // the claim re-sort's closed form at a single count crossing: 0 off, 1 LEAN Solve, 2 every Solve
+#define KS_SORT_CLOSED 1
+#endif
+#ifndef KS_SORT_OUTLINE  // the general claim re-sort as one out-of-line function per kernel (0: inlined at both call sites)
+#define KS_SORT_OUTLINE 1
+#endif
+#ifndef KS_TPL_MEMO  // LEAN Solve: a NewNodeClaim reuses what the last one derived from the same template, state, requests
+#define KS_TPL_MEMO 1
+#endif
+// LEAN Solve: 1 issues a run's queue loads for the commit log ahead of its stores (0: 64 per load).  Measured on
+// C2 at -0.09 ms of 7.55, under the round's margin of three spreads: off
+#ifndef KS_LOG_AHEAD
+#define KS_LOG_AHEAD 0
+#endif
 
 #include "ks_gosort.h"
 #include "ks_problem.h"
@@ -190,12 +204,18 @@ __device__ __forceinline__ void lds_copy(T KS_L* dst, const T KS_G* src, int n) 
 #define PHS_END(v, slot) scyc[slot] += __builtin_amdgcn_s_memtime() - v  // sub-phases (Solver member)
 #define SPHS_END(o, v, slot) o.scyc[slot] += __builtin_amdgcn_s_memtime() - v  // (from k_solve)
 #define FPH_END(v, slot) fcyc[slot] += __builtin_amdgcn_s_memtime() - v  // fine phases (k_solve, CT_FINE)
+#define XPH_END(v, slot) xcyc[slot] += __builtin_amdgcn_s_memtime() - v  // the step's sub-phases (Solver member, CT_STEP)
+#define SXPH_END(o, v, slot) o.xcyc[slot] += __builtin_amdgcn_s_memtime() - v  // (from k_solve)
+#define XPH_COUNT(slot) xcyc[slot] += 1
 #else
 #define PH_BEGIN(v)
 #define PH_END(v, slot)
 #define PHS_END(v, slot)
 #define SPHS_END(o, v, slot)
 #define FPH_END(v, slot)
+#define XPH_END(v, slot)
+#define SXPH_END(o, v, slot)
+#define XPH_COUNT(slot)
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -525,9 +545,354 @@ __global__ __launch_bounds__(256) void k_feasibility_nodes(KsDev D, int nbx) {
 // A topology simulation keeps its register window's node domains in LDS (Solver::s_tdw): the first kTdw nodes,
 // the first kTdwKeys key slots (make_plan counts the bytes).
 constexpr int kTdw = 256, kTdwKeys = 4;
+// LDS words of the LEAN Solve's NewNodeClaim memo (Solver::s_memo; make_plan counts the bytes)
+constexpr int tpl_memo_words(int R, int TW) { return TW + 6 * R + 4; }
+
+// The claim order and its re-sort: s.newNodeClaims as claim ids and pod counts per sorted position, and the
+// wave-parallel replay of Go's pdqsort_func over them.  Kept apart from Solver (which derives from it) so that the
+// general re-sort can run out of line on the two LDS arrays alone (claim_sort_general).
+struct ClaimSort {
+  LI32 s_order;         // [KO] s.newNodeClaims as claim ids
+  LI32 s_okey;          // [KO] len(Pods) of the claim at each position
+  // --- s.newNodeClaims re-sort (scheduler.go:247) --------------------------------------------------
+  // Called only when the array is not non-decreasing (a non-decreasing array is provably left
+  // untouched by pdqsort).  Lane 0 replays Go's pdqsort_func; the position-indexed quick-reject
+  // arrays are then regathered from the claims.
+  // Move the entry at position `from` to `to`, shifting the ones between by one (wave-parallel, in
+  // 64-entry chunks ordered so every chunk is read before it is overwritten).  Equals the adjacent
+  // swap chains of partialInsertionSort.
+  __device__ __forceinline__ void pis_move(int from, int to) {
+    if (from == to) return;
+    const int k0 = uni(s_okey[from]), v0 = uni(s_order[from]);
+    wsync();
+    if (to < from) {  // [to, from) shifts right, high chunk first
+      for (int hi = from; hi > to; hi -= kWave) {
+        const int lo = hi - kWave > to ? hi - kWave : to, j = lo + lane();
+        int k = 0, v = 0;
+        if (j < hi) { k = s_okey[j]; v = s_order[j]; }
+        wsync();
+        if (j < hi) { s_okey[j + 1] = k; s_order[j + 1] = v; }
+        wsync();
+      }
+    } else {  // (from, to] shifts left, low chunk first
+      for (int lo = from + 1; lo <= to; lo += kWave) {
+        const int hi = lo + kWave <= to + 1 ? lo + kWave : to + 1, j = lo + lane();
+        int k = 0, v = 0;
+        if (j < hi) { k = s_okey[j]; v = s_order[j]; }
+        wsync();
+        if (j < hi) { s_okey[j - 1] = k; s_order[j - 1] = v; }
+        wsync();
+      }
+    }
+    s_okey[to] = k0;  // wave-wide store of uniform values (see commit_claim)
+    s_order[to] = v0;
+    wsync();
+  }
+  // First i in [from, n) with key[i] < key[i-1] (a descent), or n.  Four chunks per round trip: the
+  // scan usually runs to the end of the array (proving it sorted), so it is latency-bound.
+  __device__ __forceinline__ int pis_descent(int from, int n) const {
+    for (int base = from; base < n; base += 4 * kWave) {
+      uint64_t m[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int i = base + u * kWave + lane();
+        const int k1 = i < n ? s_okey[i] : 0, k0 = i < n ? s_okey[i - 1] : 0;
+        m[u] = wballot(k1 < k0);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++)
+        if (m[u]) return base + u * kWave + ctz64(m[u]);
+    }
+    return n;
+  }
+  // choosePivot_func (zsortfunc.go): the wave reads the (up to) nine samples at once, lane t sample t,
+  // and the medians run on scalars; same pivot and hint as GoSortT::choosePivot.
+  __device__ __forceinline__ int w_choose_pivot(int a, int b, int& hint) const {
+    const int l = b - a;
+    int i = a + l / 4, j = a + l / 4 * 2, k = a + l / 4 * 3, swaps = 0;
+    if (l >= 8) {
+      const int t = lane() < 9 ? lane() : 0, g = t / 3;
+      const int pos = (g == 0 ? i : g == 1 ? j : k) + (t % 3) - 1;
+      const int key = s_okey[pos];
+      int ik[9], kk[9];
+#pragma unroll
+      for (int u = 0; u < 9; u++) {
+        ik[u] = (u / 3 == 0 ? i : u / 3 == 1 ? j : k) + (u % 3) - 1;
+        kk[u] = rdl(key, u);
+      }
+      auto median = [&](int ia, int ka, int ib, int kb, int ic, int kc, int& km) {
+        if (kb < ka) { swaps++; int t0 = ia; ia = ib; ib = t0; t0 = ka; ka = kb; kb = t0; }
+        if (kc < kb) { swaps++; int t0 = ib; ib = ic; ic = t0; t0 = kb; kb = kc; kc = t0; }
+        if (kb < ka) { swaps++; int t0 = ia; ia = ib; ib = t0; t0 = ka; ka = kb; kb = t0; }
+        km = kb;
+        return ib;
+      };
+      int ki = kk[1], kj = kk[4], kq = kk[7];
+      if (l >= 50) {
+        i = median(ik[0], kk[0], ik[1], kk[1], ik[2], kk[2], ki);
+        j = median(ik[3], kk[3], ik[4], kk[4], ik[5], kk[5], kj);
+        k = median(ik[6], kk[6], ik[7], kk[7], ik[8], kk[8], kq);
+      }
+      int km = 0;
+      j = median(i, ki, j, kj, k, kq, km);
+    }
+    hint = swaps == 0 ? 1 : (swaps == 12 ? 2 : 0);
+    return j;
+  }
+  // partialInsertionSort_func(data, 0, n) of Go 1.21 (zsortfunc.go), wave-parallel: each of its <= 5
+  // steps finds the next descent by ballot, swaps the pair, then moves the smaller entry left past
+  // every greater one and the greater entry right past every smaller one.  Returns its result and
+  // widens [tlo, thi] to the positions it moved.
+  __device__ __forceinline__ bool pis_wave(int a, int b, int& tlo, int& thi) {
+    int i = a + 1;
+    for (int step = 0; step < 5; step++) {
+      i = pis_descent(i, b);
+      if (i == b) return true;
+      if (b - a < 50) return false;
+      const int x = uni(s_okey[i]), y = uni(s_okey[i - 1]);  // after the swap: x at i-1, y at i
+      int p = i - 1;  // x passes the entries q < i-1 with x < key[q] (Go's loop runs down to index 1,
+      if (i - a >= 2) {  // not to a, once the pair is at least two past a)
+        for (int hi = i - 1; hi > 0; hi -= kWave) {
+          const int q = hi - 1 - lane();
+          const uint64_t m = wballot(q >= 0 && !(x < s_okey[q]));
+          if (m) { p = hi - ctz64(m); break; }
+          p = hi - kWave > 0 ? hi - kWave : 0;
+        }
+      }
+      int r = i;  // y passes the entries q > i with key[q] < y
+      for (int lo = i + 1; lo < b; lo += kWave) {
+        const int q = lo + lane();
+        const uint64_t m = wballot(q < b && !(s_okey[q] < y));
+        if (m) { r = lo + ctz64(m) - 1; break; }
+        r = lo + kWave - 1 < b - 1 ? lo + kWave - 1 : b - 1;
+      }
+      pis_move(i, p);  // x (at i before the swap) to p; y moves from i-1 to i with the shifted run
+      pis_move(i, r);  // y to r
+      tlo = p < tlo ? p : tlo;
+      thi = r > thi ? r : thi;
+    }
+    return false;
+  }
+
+  // --- the rest of pdqsort_func, wave-parallel and swap-for-swap equal to Go's (ks_gosort.h) -------
+  // Exchange of two uniform positions (wave-wide stores of uniform values).
+  __device__ __forceinline__ void w_swap(int i, int j) {
+    const int ki = uni(s_okey[i]), kj = uni(s_okey[j]), vi = uni(s_order[i]), vj = uni(s_order[j]);
+    wsync();
+    s_okey[i] = kj;
+    s_order[i] = vj;
+    wsync();
+    s_okey[j] = ki;
+    s_order[j] = vi;
+    wsync();
+  }
+  // Entries of [a, b) whose key is below `pk` (below_or_eq: at most `pk`).
+  __device__ __forceinline__ int w_count(int a, int b, int pk, bool below_or_eq) const {
+    int c = 0;
+    for (int base = a; base < b; base += kWave) {
+      const int p = base + lane();
+      const int k = p < b ? s_okey[p] : 0;
+      c += __popcll(wballot(p < b && (below_or_eq ? k <= pk : k < pk)));
+    }
+    return c;
+  }
+  // A Hoare pass (partition_func / partitionEqual_func) whose boundary `m` is known up front: its i scan
+  // stops on the left region's entries [l0, m) of the wrong side, its j scan on the right region's
+  // [m, r1), and it exchanges the k-th from the left with the k-th from the right, for every k (the two
+  // counts are equal, and the scans cross exactly at the boundary).  `eq` selects partitionEqual's
+  // predicates (wrong on the left: key > pk) over partition's (key >= pk).  Returns the exchange count.
+  __device__ int w_hoare(int l0, int m, int r1, int pk, bool eq) {
+    int lb = l0, rb = r1, lbase = 0, rtop = 0, swaps = 0;
+    uint64_t mL = 0, mR = 0;
+    for (;;) {
+      if (mL == 0) {
+        if (lb >= m) break;
+        const int p = lb + lane();
+        const int k = p < m ? s_okey[p] : 0;
+        mL = wballot(p < m && (eq ? k > pk : k >= pk));
+        lbase = lb;
+        lb += kWave;
+        continue;
+      }
+      if (mR == 0) {
+        if (rb <= m) break;
+        const int p = rb - 1 - lane();  // bit t <-> position rtop - t: ascending bits walk down from r1
+        const int k = p >= m ? s_okey[p] : 0;
+        mR = wballot(p >= m && (eq ? k <= pk : k < pk));
+        rtop = rb - 1;
+        rb -= kWave;
+        continue;
+      }
+      const int nL = __popcll(mL), nR = __popcll(mR), np = nL < nR ? nL : nR;
+      const uint64_t below = (1ull << lane()) - 1ull;
+      const bool inL = (mL >> lane()) & 1ull, inR = (mR >> lane()) & 1ull;
+      const int rkL = __popcll(mL & below), rkR = __popcll(mR & below);
+      // ds_permute pushes every lane's position to its rank (a bijection over the 64 lanes)
+      const int dL = inL ? rkL : nL + (lane() - rkL), dR = inR ? rkR : nR + (lane() - rkR);
+      const int posL = __builtin_amdgcn_ds_permute(dL * 4, lbase + lane());
+      const int posR = __builtin_amdgcn_ds_permute(dR * 4, rtop - lane());
+      if (lane() < np) {  // disjoint positions: the lanes' exchanges do not overlap
+        const int kl = s_okey[posL], vl = s_order[posL], kr = s_okey[posR], vr = s_order[posR];
+        s_okey[posL] = kr;
+        s_order[posL] = vr;
+        s_okey[posR] = kl;
+        s_order[posR] = vl;
+      }
+      wsync();
+      for (int t = 0; t < np; t++) {
+        mL &= mL - 1;
+        mR &= mR - 1;
+      }
+      swaps += np;
+    }
+    return swaps;
+  }
+  // partition_func: returns the new pivot position; `already` = no exchange was needed.
+  __device__ __forceinline__ int w_partition(int a, int b, int pivot, bool& already) {
+    w_swap(a, pivot);
+    const int pk = uni(s_okey[a]);
+    const int j = a + w_count(a + 1, b, pk, false);
+    already = w_hoare(a + 1, j + 1, b, pk, false) == 0;
+    w_swap(j, a);
+    return j;
+  }
+  // partitionEqual_func: returns the first position past the entries equal to the pivot.
+  __device__ __forceinline__ int w_partition_equal(int a, int b, int pivot) {
+    w_swap(a, pivot);
+    const int pk = uni(s_okey[a]);
+    const int m = a + 1 + w_count(a + 1, b, pk, true);
+    w_hoare(a + 1, m, b, pk, true);
+    return m;
+  }
+  __device__ __forceinline__ void w_reverse(int a, int b) {
+    const int h = (b - a) / 2;
+    for (int base = 0; base < h; base += kWave) {
+      const int t = base + lane();
+      if (t < h) {
+        const int i = a + t, j = b - 1 - t;
+        const int ki = s_okey[i], vi = s_order[i], kj = s_okey[j], vj = s_order[j];
+        s_okey[i] = kj;
+        s_order[i] = vj;
+        s_okey[j] = ki;
+        s_order[j] = vi;
+      }
+    }
+    wsync();
+  }
+  // GoSortExactT::run with the whole wave: frames live one per lane (lane k = stack slot k), the
+  // partitions, reversals and partialInsertionSorts run wave-parallel; insertionSort (<= 12 entries),
+  // heapSort (the depth limit), breakPatterns and choosePivot stay on lane 0.  resumePivot as in run().
+  __device__ void w_pdqsort(int n, int resumePivot) {
+    int fa = 0, fb = 0, fl = 0, ff = 0;  // this lane's stack slot: a, b, limit, flags (wb | wp << 1)
+    int sp = 0;
+    {
+      const bool me = lane() == 0;
+      fa = me ? 0 : fa;
+      fb = me ? n : fb;
+      fl = me ? GoSortT<LI32>::bitsLen((uint32_t)n) : fl;
+      ff = me ? 3 : ff;
+      sp = 1;
+    }
+    bool resume = resumePivot >= 0;
+    int dummy_lo = 0, dummy_hi = 0;
+    while (sp > 0) {
+      sp--;
+      int a = rdl(fa, sp), b = rdl(fb, sp), limit = rdl(fl, sp);
+      const int flags = rdl(ff, sp);
+      bool wasBalanced = flags & 1, wasPartitioned = (flags >> 1) & 1;
+      for (;;) {
+        const int length = b - a;
+        int pivot;
+        if (resume) {
+          resume = false;
+          pivot = resumePivot;
+        } else {
+          if (length <= 12 || limit == 0) {
+            if (lane() == 0) {
+              GoSortT<LI32> g{s_okey, s_order};
+              if (length <= 12) g.insertionSort(a, b);
+              else g.heapSort(a, b);
+            }
+            wsync();
+            break;
+          }
+          if (!wasBalanced) {
+            if (lane() == 0) {
+              GoSortT<LI32> g{s_okey, s_order};
+              g.breakPatterns(a, b);
+            }
+            wsync();
+            limit--;
+          }
+          int hint = 0;
+          pivot = w_choose_pivot(a, b, hint);
+          if (hint == 2) {
+            w_reverse(a, b);
+            pivot = (b - 1) - (pivot - a);
+            hint = 1;
+          }
+          if (wasBalanced && wasPartitioned && hint == 1 && pis_wave(a, b, dummy_lo, dummy_hi)) break;
+        }
+        if (a > 0 && ub(!(s_okey[a - 1] < s_okey[pivot]))) {
+          a = w_partition_equal(a, b, pivot);
+          continue;
+        }
+        bool already = false;
+        const int mid = w_partition(a, b, pivot, already);
+        wasPartitioned = already;
+        const int leftLen = mid - a, rightLen = b - mid, thr = length / 8;
+        if (sp + 2 > kWave) return;  // unreachable: depth <= 2*log2(n) + 2
+        int c0a, c0b, c1a, c1b;
+        if (leftLen < rightLen) {
+          wasBalanced = leftLen >= thr;
+          c0a = mid + 1; c0b = b; c1a = a; c1b = mid;  // continuation, then the recursive call
+        } else {
+          wasBalanced = rightLen >= thr;
+          c0a = a; c0b = mid; c1a = mid + 1; c1b = b;
+        }
+        const bool m0 = lane() == sp, m1 = lane() == sp + 1;
+        fa = m0 ? c0a : (m1 ? c1a : fa);
+        fb = m0 ? c0b : (m1 ? c1b : fb);
+        fl = (m0 || m1) ? limit : fl;
+        ff = m0 ? ((int)wasBalanced | ((int)wasPartitioned << 1)) : (m1 ? 3 : ff);
+        sp += 2;
+        break;
+      }
+    }
+  }
+};
+// The general re-sort: partialInsertionSort when choosePivot gave the increasing hint (pivot >= 0), else or after
+// it the exact pdqsort.  claim_sort_general_out is the same out of line (KS_SORT_OUTLINE), so a kernel holds one copy
+// for its two call sites; the arguments are the two LDS arrays, not the Solver (a pointer to which would force its
+// state into memory).
+// Returns tlo | (thi + 1) << 15 | done << 30 (positions < 2^14: KsDims::Kcap).
+static __device__ __forceinline__ uint32_t claim_sort_general(LI32 okey, LI32 order, int n, int pivot) {
+  ClaimSort cs;
+  cs.s_order = order;
+  cs.s_okey = okey;
+  int tlo = n, thi = -1;
+  bool done = false;
+  if (pivot >= 0) done = cs.pis_wave(0, n, tlo, thi);
+  if (!done) {
+#if KS_SORT_LANE0
+    if (lane() == 0) {
+      GoSortExactT<LI32> g{GoSortT<LI32>{okey, order}};
+      g.run(n, pivot);
+    }
+#else
+    cs.w_pdqsort(n, pivot);
+#endif
+    tlo = 0;
+    thi = n - 1;
+  }
+  return (uint32_t)tlo | (uint32_t)(thi + 1) << 15 | (uint32_t)done << 30;
+}
+static __device__ __noinline__ uint32_t claim_sort_general_out(LI32 okey, LI32 order, int n, int pivot) {
+  return claim_sort_general(okey, order, n, pivot);
+}
 
 template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN>
-struct Solver {
+struct Solver : ClaimSort {
   static constexpr int RM = RT > 0 ? RT : kMaxR;
   // LEAN: the problem uses none of host ports, limited volumes, pod label requirements, shared UIDs,
   // negative requests or topology (KsDims::lean, set by the encoder).  Those paths compile out, which
@@ -551,8 +916,6 @@ struct Solver {
   DevLayout L;
   ClaimView<true> lc;   // claims [0, KL)
   ClaimView<false> gc;  // claims [KL, KO)
-  LI32 s_order;         // [KO] s.newNodeClaims as claim ids
-  LI32 s_okey;          // [KO] len(Pods) of the claim at each position
   LI32 s_ptpl;          // [KO] template of the claim at each position
   LI64 s_phead;         // [KO][R] max Allocatable - requests of the claim at each position
   LI64 s_talloc;        // [totalTplIts][R] Allocatable per template position (pl.talloc)
@@ -567,6 +930,12 @@ struct Solver {
   LU32 s_fic;           // [TW+2] feas_masks: Intersects(IT, X) per position
   LU32 s_fof;           // [TW+2] feas_masks: hasOffering(IT, X) per position
   LU32 s_firr;          // [TW+2] feas_masks: irregular positions (exact per-position check)
+  // LEAN Solve (KS_TPL_MEMO): what the last NewNodeClaim from a template without a NodePool limit derived, keyed by
+  // (template, pod requests): options, thresholds, option count, max Allocatable (try_templates)
+  enum : int { MM_T = 0, MM_CNT, MM_POD = 4 };  // then [R] pod, [R] max (int64), [R] thr, [TW] options
+  static constexpr bool TPL_MEMO = KS_TPL_MEMO && LEAN && !SIM;
+  LU32 s_memo;          // [tpl_memo_words]
+  int64_t memoHits = 0;
   LU32 s_rmv;           // SIM: [ceil(N/32)] nodes removed by the simulation (the candidates)
   LU32 s_tch;           // SIM: [ceil(N/32)] nodes whose requests live in a W.n_req slot
   LU32 s_tchr;          // SIM: [ceil(N/32)] nodes whose requirements live in a W.n_rs slot; Solve (d.fnOn): nodes
@@ -607,6 +976,7 @@ struct Solver {
   LI32 s_vol;
 #ifdef KS_PHASE_STATS
   mutable uint64_t scyc[4] = {0, 0, 0, 0};  // claim_full sub-phases: requirements, thresholds, masks, apply
+  mutable uint64_t xcyc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the step's sub-phases (StepSub)
 #endif
 
   __device__ Solver(const KsDev& D_, const KsWork KS_C& W_, const Plan& p_) : D(D_), d(D_.d), W(W_), pl(p_) {}
@@ -1842,9 +2212,27 @@ struct Solver {
       int hostid = -1;
       const int tb = s_tbeg[t], nIT = s_tbeg[t + 1] - tb;
       const int pool = D.tpl_pool[t];
+      PH_BEGIN(ttd);
+      // KS_TPL_MEMO: without a NodePool limit the options, thresholds, option count and max Allocatable of a fresh
+      // NodeClaim are a function of (t, pod): every instance type is a candidate, the requirements are the
+      // template's (LEAN pods carry no keys and no topology), Fits tests tpl_daemon[t] + pod against static tables.
+      // The state s -- one per pod, never shared -- enters only through k_feasibility's row (s, t), which a LEAN
+      // problem does not have (fmOn needs a state with keys, KsDims::lean none; fm_row is then null for every s):
+      // the memo is bypassed should the rows ever be on.  The last claim created that way is kept in LDS; an equal
+      // key takes its values (it was created before, so it is no failure path) and runs everything else -- the
+      // NewNodeClaim counter, the taint test, the claim cap, every store, the log, the algorithmic bytes.
+      bool hit = false;
+      if constexpr (TPL_MEMO) {
+        if (pool < 0 && !d.fmOn) {
+          hit = (int)s_memo[MM_T] == t;  // (uniform reads)
+          const LI64 mp = (LI64)(s_memo + MM_POD);
+          for (int r = 0; r < R(); r++) hit = hit && mp[r] == pod[r];
+          hit = ub(hit);
+        }
+      }
       // filterByRemainingResources (scheduler.go:364-383)
       uint64_t anyCand = 0;
-      for (int base = 0; base < nIT; base += kWave) {
+      for (int base = 0; base < (hit ? 0 : nIT); base += kWave) {
         const int pos = base + lane();
         bool ok = pos < nIT;
         if (ok && pool >= 0) {
@@ -1897,8 +2285,13 @@ struct Solver {
             for (int r = 0; r < R(); r++) req[r] = D.tpl_daemon[(int64_t)t * R() + r] + pod[r];
             uint32_t flags = 0;
             uint64_t any = 0;
-            feas_masks(s_rs, t, fm_row(s, t));
-            for (int base = 0; base < nIT; base += kWave) {
+            if (hit) {  // the memo's options
+              copy_words(s_rem, s_memo + MM_POD + 5 * R(), d.TW);
+              any = 1;
+            } else {
+              feas_masks(s_rs, t, fm_row(s, t));
+            }
+            for (int base = 0; base < (hit ? 0 : nIT); base += kWave) {
               const int pos = base + lane();
               const bool in = pos < nIT && ((s_cand[pos >> 5] >> (pos & 31)) & 1u);
               bool ic = false, fi = false, of = false;
@@ -1934,22 +2327,32 @@ struct Solver {
             } else {
               if (nclaims >= pl.KO) return -1;
               const int c = nclaims++;
+              XPH_END(ttd, SS_TPL_DERIVE);
+              PH_BEGIN(tts0);
               if (SIM && TOPO)  // the next fresh claim's placeholder counts (a simulation zeroes one column per claim)
                 for (int g = lane(); g < d.G; g += kWave) W.tg_ccnt[(int64_t)g * W.ccs + nclaims] = 0;
               const bool inl = c < pl.KL;
               copy_words(W.c_rs + (int64_t)c * d.RSW, s_rs, d.RSW);
               if (inl) copy_words(lc.rem + (int64_t)c * d.TW, s_rem, d.TW);
               else copy_words(gc.rem + (int64_t)c * d.TW, s_rem, d.TW);
+              XPH_END(tts0, SS_TPL_STORE);
+              PH_BEGIN(ttd1);
               // thresholds: how much of each resource's ascending Allocatable order req excludes
               int thr[RM];
               for (int r = 0; r < R(); r++) {
+                if (hit) {
+                  thr[r] = uni((int)s_memo[MM_POD + 4 * R() + r]);
+                  continue;
+                }
                 const int64_t b = (int64_t)tb * R() + (int64_t)r * nIT;
                 int k = 0;
                 for (int q = 0; q < nIT; q += kWave)
                   k += __popcll(wballot(q + lane() < nIT && tsort_a(b + q + lane()) < req[r]));
                 thr[r] = k;
               }
-              const int cnt = popc_words(s_rem, d.TW);
+              const int cnt = hit ? uni((int)s_memo[MM_CNT]) : popc_words(s_rem, d.TW);
+              XPH_END(ttd1, SS_TPL_DERIVE);
+              PH_BEGIN(tts1);
               // wave-wide stores of uniform values (see commit_claim)
               for (int r = 0; r < R(); r++) {
                 if (inl) {
@@ -1976,9 +2379,39 @@ struct Solver {
               log_commit(p, c, nlog);
               hbm_release();  // c_rs / c_tpl / overflow state are read by other lanes later
               wsync();
+              XPH_END(tts1, SS_TPL_STORE);
               if (TOPO && t_rec) topo_record(s_rs, c, -1, d.allowWK, nlog - 1);
-              if (inl) recompute_max<true>(c, s_rem, t, c);
-              else recompute_max<false>(c, s_rem, t, c);
+              PH_BEGIN(ttm);
+              if (hit) {  // recompute_max's stores with the memo's values
+                const LI64 mx = (LI64)(s_memo + MM_POD + 2 * R());
+                for (int r = 0; r < R(); r++) {
+                  const int64_t m = uni64(mx[r]);
+                  if (inl) lc.max[(int64_t)c * R() + r] = m;
+                  else gc.max[(int64_t)c * R() + r] = m;
+                  s_phead[(int64_t)c * R() + r] = m - req[r];
+                }
+                if (!inl) hbm_release();
+                wsync();
+                memoHits++;
+              } else {
+                if (inl) recompute_max<true>(c, s_rem, t, c);
+                else recompute_max<false>(c, s_rem, t, c);
+                if constexpr (TPL_MEMO) {
+                  if (pool < 0 && !d.fmOn) {  // keep what this claim derived (wave-wide stores of uniform values)
+                    const LI64 mp = (LI64)(s_memo + MM_POD);
+                    for (int r = 0; r < R(); r++) {
+                      mp[r] = pod[r];
+                      mp[R() + r] = inl ? uni64(lc.max[(int64_t)c * R() + r]) : uni64(ld_sc1(gc.max + (int64_t)c * R() + r));
+                      s_memo[MM_POD + 4 * R() + r] = (uint32_t)thr[r];
+                    }
+                    copy_words(s_memo + MM_POD + 5 * R(), s_rem, d.TW);
+                    s_memo[MM_T] = (uint32_t)t;
+                    s_memo[MM_CNT] = (uint32_t)cnt;
+                    wsync();
+                  }
+                }
+              }
+              XPH_END(ttm, SS_TPL_MAX);
               if (pool >= 0) {  // subtractMax (scheduler.go:347-362)
                 const uint32_t mask = D.pool_mask[pool];
                 for (int r = 0; r < R(); r++) {
@@ -2033,335 +2466,69 @@ struct Solver {
     return 0;
   }
 
-  // --- s.newNodeClaims re-sort (scheduler.go:247) --------------------------------------------------
-  // Called only when the array is not non-decreasing (a non-decreasing array is provably left
-  // untouched by pdqsort).  Lane 0 replays Go's pdqsort_func; the position-indexed quick-reject
-  // arrays are then regathered from the claims.
-  // Move the entry at position `from` to `to`, shifting the ones between by one (wave-parallel, in
-  // 64-entry chunks ordered so every chunk is read before it is overwritten).  Equals the adjacent
-  // swap chains of partialInsertionSort.
-  __device__ __forceinline__ void pis_move(int from, int to) {
-    if (from == to) return;
-    const int k0 = uni(s_okey[from]), v0 = uni(s_order[from]);
-    wsync();
-    if (to < from) {  // [to, from) shifts right, high chunk first
-      for (int hi = from; hi > to; hi -= kWave) {
-        const int lo = hi - kWave > to ? hi - kWave : to, j = lo + lane();
-        int k = 0, v = 0;
-        if (j < hi) { k = s_okey[j]; v = s_order[j]; }
-        wsync();
-        if (j < hi) { s_okey[j + 1] = k; s_order[j + 1] = v; }
-        wsync();
-      }
-    } else {  // (from, to] shifts left, low chunk first
-      for (int lo = from + 1; lo <= to; lo += kWave) {
-        const int hi = lo + kWave <= to + 1 ? lo + kWave : to + 1, j = lo + lane();
-        int k = 0, v = 0;
-        if (j < hi) { k = s_okey[j]; v = s_order[j]; }
-        wsync();
-        if (j < hi) { s_okey[j - 1] = k; s_order[j - 1] = v; }
-        wsync();
-      }
-    }
-    s_okey[to] = k0;  // wave-wide store of uniform values (see commit_claim)
-    s_order[to] = v0;
-    wsync();
-  }
-  // First i in [from, n) with key[i] < key[i-1] (a descent), or n.  Four chunks per round trip: the
-  // scan usually runs to the end of the array (proving it sorted), so it is latency-bound.
-  __device__ __forceinline__ int pis_descent(int from, int n) const {
-    for (int base = from; base < n; base += 4 * kWave) {
-      uint64_t m[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int i = base + u * kWave + lane();
-        const int k1 = i < n ? s_okey[i] : 0, k0 = i < n ? s_okey[i - 1] : 0;
-        m[u] = wballot(k1 < k0);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++)
-        if (m[u]) return base + u * kWave + ctz64(m[u]);
-    }
-    return n;
-  }
-  // choosePivot_func (zsortfunc.go): the wave reads the (up to) nine samples at once, lane t sample t,
-  // and the medians run on scalars; same pivot and hint as GoSortT::choosePivot.
-  __device__ __forceinline__ int w_choose_pivot(int a, int b, int& hint) const {
-    const int l = b - a;
-    int i = a + l / 4, j = a + l / 4 * 2, k = a + l / 4 * 3, swaps = 0;
-    if (l >= 8) {
-      const int t = lane() < 9 ? lane() : 0, g = t / 3;
-      const int pos = (g == 0 ? i : g == 1 ? j : k) + (t % 3) - 1;
-      const int key = s_okey[pos];
-      int ik[9], kk[9];
-#pragma unroll
-      for (int u = 0; u < 9; u++) {
-        ik[u] = (u / 3 == 0 ? i : u / 3 == 1 ? j : k) + (u % 3) - 1;
-        kk[u] = rdl(key, u);
-      }
-      auto median = [&](int ia, int ka, int ib, int kb, int ic, int kc, int& km) {
-        if (kb < ka) { swaps++; int t0 = ia; ia = ib; ib = t0; t0 = ka; ka = kb; kb = t0; }
-        if (kc < kb) { swaps++; int t0 = ib; ib = ic; ic = t0; t0 = kb; kb = kc; kc = t0; }
-        if (kb < ka) { swaps++; int t0 = ia; ia = ib; ib = t0; t0 = ka; ka = kb; kb = t0; }
-        km = kb;
-        return ib;
-      };
-      int ki = kk[1], kj = kk[4], kq = kk[7];
-      if (l >= 50) {
-        i = median(ik[0], kk[0], ik[1], kk[1], ik[2], kk[2], ki);
-        j = median(ik[3], kk[3], ik[4], kk[4], ik[5], kk[5], kj);
-        k = median(ik[6], kk[6], ik[7], kk[7], ik[8], kk[8], kq);
-      }
-      int km = 0;
-      j = median(i, ki, j, kj, k, kq, km);
-    }
-    hint = swaps == 0 ? 1 : (swaps == 12 ? 2 : 0);
-    return j;
-  }
-  // partialInsertionSort_func(data, 0, n) of Go 1.21 (zsortfunc.go), wave-parallel: each of its <= 5
-  // steps finds the next descent by ballot, swaps the pair, then moves the smaller entry left past
-  // every greater one and the greater entry right past every smaller one.  Returns its result and
-  // widens [tlo, thi] to the positions it moved.
-  __device__ __forceinline__ bool pis_wave(int a, int b, int& tlo, int& thi) {
-    int i = a + 1;
-    for (int step = 0; step < 5; step++) {
-      i = pis_descent(i, b);
-      if (i == b) return true;
-      if (b - a < 50) return false;
-      const int x = uni(s_okey[i]), y = uni(s_okey[i - 1]);  // after the swap: x at i-1, y at i
-      int p = i - 1;  // x passes the entries q < i-1 with x < key[q] (Go's loop runs down to index 1,
-      if (i - a >= 2) {  // not to a, once the pair is at least two past a)
-        for (int hi = i - 1; hi > 0; hi -= kWave) {
-          const int q = hi - 1 - lane();
-          const uint64_t m = wballot(q >= 0 && !(x < s_okey[q]));
-          if (m) { p = hi - ctz64(m); break; }
-          p = hi - kWave > 0 ? hi - kWave : 0;
-        }
-      }
-      int r = i;  // y passes the entries q > i with key[q] < y
-      for (int lo = i + 1; lo < b; lo += kWave) {
-        const int q = lo + lane();
-        const uint64_t m = wballot(q < b && !(s_okey[q] < y));
-        if (m) { r = lo + ctz64(m) - 1; break; }
-        r = lo + kWave - 1 < b - 1 ? lo + kWave - 1 : b - 1;
-      }
-      pis_move(i, p);  // x (at i before the swap) to p; y moves from i-1 to i with the shifted run
-      pis_move(i, r);  // y to r
-      tlo = p < tlo ? p : tlo;
-      thi = r > thi ? r : thi;
-    }
-    return false;
-  }
-
-  // --- the rest of pdqsort_func, wave-parallel and swap-for-swap equal to Go's (ks_gosort.h) -------
-  // Exchange of two uniform positions (wave-wide stores of uniform values).
-  __device__ __forceinline__ void w_swap(int i, int j) {
-    const int ki = uni(s_okey[i]), kj = uni(s_okey[j]), vi = uni(s_order[i]), vj = uni(s_order[j]);
-    wsync();
-    s_okey[i] = kj;
-    s_order[i] = vj;
-    wsync();
-    s_okey[j] = ki;
-    s_order[j] = vi;
-    wsync();
-  }
-  // Entries of [a, b) whose key is below `pk` (below_or_eq: at most `pk`).
-  __device__ __forceinline__ int w_count(int a, int b, int pk, bool below_or_eq) const {
-    int c = 0;
-    for (int base = a; base < b; base += kWave) {
-      const int p = base + lane();
-      const int k = p < b ? s_okey[p] : 0;
-      c += __popcll(wballot(p < b && (below_or_eq ? k <= pk : k < pk)));
-    }
-    return c;
-  }
-  // A Hoare pass (partition_func / partitionEqual_func) whose boundary `m` is known up front: its i scan
-  // stops on the left region's entries [l0, m) of the wrong side, its j scan on the right region's
-  // [m, r1), and it exchanges the k-th from the left with the k-th from the right, for every k (the two
-  // counts are equal, and the scans cross exactly at the boundary).  `eq` selects partitionEqual's
-  // predicates (wrong on the left: key > pk) over partition's (key >= pk).  Returns the exchange count.
-  __device__ int w_hoare(int l0, int m, int r1, int pk, bool eq) {
-    int lb = l0, rb = r1, lbase = 0, rtop = 0, swaps = 0;
-    uint64_t mL = 0, mR = 0;
-    for (;;) {
-      if (mL == 0) {
-        if (lb >= m) break;
-        const int p = lb + lane();
-        const int k = p < m ? s_okey[p] : 0;
-        mL = wballot(p < m && (eq ? k > pk : k >= pk));
-        lbase = lb;
-        lb += kWave;
-        continue;
-      }
-      if (mR == 0) {
-        if (rb <= m) break;
-        const int p = rb - 1 - lane();  // bit t <-> position rtop - t: ascending bits walk down from r1
-        const int k = p >= m ? s_okey[p] : 0;
-        mR = wballot(p >= m && (eq ? k <= pk : k < pk));
-        rtop = rb - 1;
-        rb -= kWave;
-        continue;
-      }
-      const int nL = __popcll(mL), nR = __popcll(mR), np = nL < nR ? nL : nR;
-      const uint64_t below = (1ull << lane()) - 1ull;
-      const bool inL = (mL >> lane()) & 1ull, inR = (mR >> lane()) & 1ull;
-      const int rkL = __popcll(mL & below), rkR = __popcll(mR & below);
-      // ds_permute pushes every lane's position to its rank (a bijection over the 64 lanes)
-      const int dL = inL ? rkL : nL + (lane() - rkL), dR = inR ? rkR : nR + (lane() - rkR);
-      const int posL = __builtin_amdgcn_ds_permute(dL * 4, lbase + lane());
-      const int posR = __builtin_amdgcn_ds_permute(dR * 4, rtop - lane());
-      if (lane() < np) {  // disjoint positions: the lanes' exchanges do not overlap
-        const int kl = s_okey[posL], vl = s_order[posL], kr = s_okey[posR], vr = s_order[posR];
-        s_okey[posL] = kr;
-        s_order[posL] = vr;
-        s_okey[posR] = kl;
-        s_order[posR] = vl;
-      }
-      wsync();
-      for (int t = 0; t < np; t++) {
-        mL &= mL - 1;
-        mR &= mR - 1;
-      }
-      swaps += np;
-    }
-    return swaps;
-  }
-  // partition_func: returns the new pivot position; `already` = no exchange was needed.
-  __device__ __forceinline__ int w_partition(int a, int b, int pivot, bool& already) {
-    w_swap(a, pivot);
-    const int pk = uni(s_okey[a]);
-    const int j = a + w_count(a + 1, b, pk, false);
-    already = w_hoare(a + 1, j + 1, b, pk, false) == 0;
-    w_swap(j, a);
-    return j;
-  }
-  // partitionEqual_func: returns the first position past the entries equal to the pivot.
-  __device__ __forceinline__ int w_partition_equal(int a, int b, int pivot) {
-    w_swap(a, pivot);
-    const int pk = uni(s_okey[a]);
-    const int m = a + 1 + w_count(a + 1, b, pk, true);
-    w_hoare(a + 1, m, b, pk, true);
-    return m;
-  }
-  __device__ __forceinline__ void w_reverse(int a, int b) {
-    const int h = (b - a) / 2;
-    for (int base = 0; base < h; base += kWave) {
-      const int t = base + lane();
-      if (t < h) {
-        const int i = a + t, j = b - 1 - t;
-        const int ki = s_okey[i], vi = s_order[i], kj = s_okey[j], vj = s_order[j];
-        s_okey[i] = kj;
-        s_order[i] = vj;
-        s_okey[j] = ki;
-        s_order[j] = vi;
-      }
-    }
-    wsync();
-  }
-  // GoSortExactT::run with the whole wave: frames live one per lane (lane k = stack slot k), the
-  // partitions, reversals and partialInsertionSorts run wave-parallel; insertionSort (<= 12 entries),
-  // heapSort (the depth limit), breakPatterns and choosePivot stay on lane 0.  resumePivot as in run().
-  __device__ void w_pdqsort(int n, int resumePivot) {
-    int fa = 0, fb = 0, fl = 0, ff = 0;  // this lane's stack slot: a, b, limit, flags (wb | wp << 1)
-    int sp = 0;
-    {
-      const bool me = lane() == 0;
-      fa = me ? 0 : fa;
-      fb = me ? n : fb;
-      fl = me ? GoSortT<LI32>::bitsLen((uint32_t)n) : fl;
-      ff = me ? 3 : ff;
-      sp = 1;
-    }
-    bool resume = resumePivot >= 0;
-    int dummy_lo = 0, dummy_hi = 0;
-    while (sp > 0) {
-      sp--;
-      int a = rdl(fa, sp), b = rdl(fb, sp), limit = rdl(fl, sp);
-      const int flags = rdl(ff, sp);
-      bool wasBalanced = flags & 1, wasPartitioned = (flags >> 1) & 1;
-      for (;;) {
-        const int length = b - a;
-        int pivot;
-        if (resume) {
-          resume = false;
-          pivot = resumePivot;
-        } else {
-          if (length <= 12 || limit == 0) {
-            if (lane() == 0) {
-              GoSortT<LI32> g{s_okey, s_order};
-              if (length <= 12) g.insertionSort(a, b);
-              else g.heapSort(a, b);
-            }
-            wsync();
-            break;
-          }
-          if (!wasBalanced) {
-            if (lane() == 0) {
-              GoSortT<LI32> g{s_okey, s_order};
-              g.breakPatterns(a, b);
-            }
-            wsync();
-            limit--;
-          }
-          int hint = 0;
-          pivot = w_choose_pivot(a, b, hint);
-          if (hint == 2) {
-            w_reverse(a, b);
-            pivot = (b - 1) - (pivot - a);
-            hint = 1;
-          }
-          if (wasBalanced && wasPartitioned && hint == 1 && pis_wave(a, b, dummy_lo, dummy_hi)) break;
-        }
-        if (a > 0 && ub(!(s_okey[a - 1] < s_okey[pivot]))) {
-          a = w_partition_equal(a, b, pivot);
-          continue;
-        }
-        bool already = false;
-        const int mid = w_partition(a, b, pivot, already);
-        wasPartitioned = already;
-        const int leftLen = mid - a, rightLen = b - mid, thr = length / 8;
-        if (sp + 2 > kWave) return;  // unreachable: depth <= 2*log2(n) + 2
-        int c0a, c0b, c1a, c1b;
-        if (leftLen < rightLen) {
-          wasBalanced = leftLen >= thr;
-          c0a = mid + 1; c0b = b; c1a = a; c1b = mid;  // continuation, then the recursive call
-        } else {
-          wasBalanced = rightLen >= thr;
-          c0a = a; c0b = mid; c1a = mid + 1; c1b = b;
-        }
-        const bool m0 = lane() == sp, m1 = lane() == sp + 1;
-        fa = m0 ? c0a : (m1 ? c1a : fa);
-        fb = m0 ? c0b : (m1 ? c1b : fb);
-        fl = (m0 || m1) ? limit : fl;
-        ff = m0 ? ((int)wasBalanced | ((int)wasPartitioned << 1)) : (m1 ? 3 : ff);
-        sp += 2;
-        break;
-      }
-    }
-  }
-  // Returns true when lane 0 ran the exact pdqsort (the wave-parallel fast path did not finish it).
-  __device__ __forceinline__ bool sort_claims(int n) {
+  // Returns how it was done: SORT_FAST (the wave-parallel partialInsertionSort finished it), SORT_EXACT (the
+  // exact pdqsort ran) or SORT_CLOSED.  `pos`: the sorted position whose count increment left the descent, -1
+  // when it has another origin (an appended claim) -- used only where the closed form is compiled in
+  // (KS_SORT_CLOSED); `npos`: where that claim went (SORT_CLOSED), else -1.
+  enum : int { SORT_FAST = 0, SORT_EXACT = 1, SORT_CLOSED_FORM = 2 };
+  static constexpr bool SORT_CLOSED = !SIM && (KS_SORT_CLOSED == 2 || (KS_SORT_CLOSED == 1 && LEAN));
+  __device__ __forceinline__ int sort_claims(int n, int pos, int& npos) {
     int tlo = n, thi = -1, pivot = -1;
     bool done = false;
+    PH_BEGIN(tsc);
+#ifdef KS_PHASE_STATS
+    if (n <= 12) XPH_COUNT(SS_SORTS_LE12);
+    else if (n < 50) XPH_COUNT(SS_SORTS_LT50);
+#endif
+    bool closed = false;
+    npos = -1;
     if (n > 12) {  // pdqsort_func's top-level frame: choosePivot (reads only), then partialInsertionSort
       int hint = 0;
       const int pv = w_choose_pivot(0, n, hint);
       if (hint == 1) {
         pivot = pv;
-        done = pis_wave(0, n, tlo, thi);
+        if constexpr (SORT_CLOSED) {
+          // The descent is the one a count increment at `pos` left: non-decreasing but key[pos] > key[pos+1].
+          // partialInsertionSort then swaps the pair, finds nothing to move left (key[pos+1] >= key[pos] - 1 >=
+          // key[pos-1]), walks the claim right past the t entries below its key and meets no second descent:
+          // (pos, pos+t] moves one place left, the claim lands at pos + t (tests/test_sort_single_descent.py).
+          // The entries past pos are sorted, so those below the key are the first t of them.
+          if (pos >= 0 && n >= 50 && pos + 1 < n) {
+            const int K = uni(s_okey[pos]);
+            if (K > uni(s_okey[pos + 1])) {
+              int t = 0;
+              for (int base = pos + 1; base < n; base += 4 * kWave) {  // four chunks per round trip (pis_descent)
+                uint64_t m[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                  const int q = base + u * kWave + lane();
+                  m[u] = wballot(q < n && s_okey[q] < K);
+                }
+                bool end = false;
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                  t += end ? 0 : popc64(m[u]);
+                  end = end || m[u] != ~0ull;
+                }
+                if (end) break;
+              }
+              pis_move(pos, pos + t);
+              tlo = pos;
+              thi = npos = pos + t;
+              done = closed = true;
+            }
+          }
+        }
       }
     }
-    if (!done) {
-#if KS_SORT_LANE0
-      if (lane() == 0) {
-        GoSortExactT<LI32> g{GoSortT<LI32>{s_okey, s_order}};
-        g.run(n, pivot);
-      }
-#else
-      w_pdqsort(n, pivot);
-#endif
-      tlo = 0;
-      thi = n - 1;
+    if (!closed) {
+      // (out of line in the LEAN Solve, whose closed form leaves this the rare path; the other instantiations
+      // keep it inlined, as measured before)
+      const uint32_t g = KS_SORT_OUTLINE && LEAN && !SIM ? claim_sort_general_out(s_okey, s_order, n, pivot)
+                                                          : claim_sort_general(s_okey, s_order, n, pivot);
+      tlo = (int)(g & 0x7fff);
+      thi = (int)(g >> 15 & 0x7fff) - 1;
+      done = g >> 30 & 1;
     }
     wsync();
     for (int j = tlo + lane(); j <= thi; j += kWave) {
@@ -2375,7 +2542,12 @@ struct Solver {
     }
     wsync();
     algbytes += (int64_t)(thi - tlo + 1) * (8 + 16 * R());
-    return !done;
+#ifdef KS_PHASE_STATS
+    if (closed) XPH_END(tsc, SS_SORT_CLOSED);
+    else if (done) XPH_END(tsc, SS_SORT_FAST);
+    else XPH_END(tsc, SS_SORT_EXACT);
+#endif
+    return closed ? SORT_CLOSED_FORM : done ? SORT_FAST : SORT_EXACT;
   }
 
   // --- consolidation decision for this simulation (SIM epilogue) -------------------------------
@@ -2873,6 +3045,7 @@ static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO,
   const size_t R = d.R, TW = d.TW, tot = d.totalTplIts;
   const size_t fixed = r16(sizeof(KeyMeta) * d.NK) + r16(4 * (size_t)(d.NTPL + 1)) + r16(8 * (size_t)(d.NPOOL + 1) * R) +
                        2 * r16(4 * (size_t)d.RSW) + 5 * r16(4 * TW + 8) + 16 * 16 + (d.volAny ? 48 : 0) +
+                       (KS_TPL_MEMO && !sim && d.lean ? r16(4 * (size_t)tpl_memo_words((int)R, (int)TW)) : 0) +
                        (sim ? 4 * r16(4 * (size_t)((d.N + 31) / 32)) : d.fnOn ? r16(4 * (size_t)((d.N + 31) / 32)) : 0) +
                        (d.G ? r16(4 * (size_t)d.G * TGM_WORDS) + r16(4 * (size_t)d.G) + 2 * r16(4 * (size_t)d.RSW) +
                                   (d.GMW > 1 ? r16(8 * (size_t)GS_N * d.GMW) : 0) +

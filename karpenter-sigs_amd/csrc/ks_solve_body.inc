@@ -49,6 +49,9 @@
   S.s_fic = (LU32)take(4 * (size_t)d.TW + 8);
   S.s_fof = (LU32)take(4 * (size_t)d.TW + 8);
   S.s_firr = (LU32)take(4 * (size_t)d.TW + 8);
+  constexpr bool MEMO = Solver<RT, TL, SIM, TOPO, LEAN>::TPL_MEMO;
+  S.s_memo = (LU32)take(MEMO ? 4 * (size_t)tpl_memo_words(R, d.TW) : 0);
+  if constexpr (MEMO) S.s_memo[S.MM_T] = (uint32_t)-1;  // empty (wave-wide store of a uniform value)
   const int NWN = (d.N + 31) >> 5;
   S.s_rmv = (LU32)take(SIM ? 4 * (size_t)NWN : 0);
   S.s_tch = (LU32)take(SIM ? 4 * (size_t)NWN : 0);
@@ -264,6 +267,11 @@
   bool allSched = true;  // SIM: AllNonPendingPodsScheduled so far (pods placed on unusable nodes)
   int nrs = 0;           // SIM: compact node-requirement slots in use
   bool srt = true;      // s.newNodeClaims non-decreasing in len(Pods)
+  // the sorted position whose count increment left the pending descent (!srt); -1: an appended claim, or not
+  // tracked (sort_claims' closed form, KS_SORT_CLOSED)
+  constexpr bool SORTC = Solver<RT, TL, SIM, TOPO, LEAN>::SORT_CLOSED;
+  int dpos = -1;
+  int64_t sortsClosed = 0;
   bool pushed = false;  // a failed pod was pushed back since the last window refill
   // no pod was pushed back yet (refill reads the pods' first states directly); a probe re-run from carried pods
   // starts with its queue state written (its pods' starting states are not all the first ones)
@@ -835,9 +843,13 @@
       pendSortB = 0;
       if (!U(srt)) {
         const int64_t ab = S.algbytes;
-        exact += S.sort_claims(nclaims);
+        int npos;
+        const int how = S.sort_claims(nclaims, SORTC ? dpos : -1, npos);
+        exact += how == S.SORT_EXACT;
+        sortsClosed += how == S.SORT_CLOSED_FORM;
         slow++;
         srt = true;
+        dpos = -1;
         sortB += S.algbytes - ab;
       }
       PH_END(t2, 2);
@@ -864,6 +876,7 @@
             srt = U(inl ? S.template commit_claim<true>(c, jj, nclaims, p, sflags, pod, req, nthr, ncnt, nlog)
                          : S.template commit_claim<false>(c, jj, nclaims, p, sflags, pod, req, nthr, ncnt, nlog));
             placed = true;
+            if constexpr (SORTC) dpos = srt ? -1 : jj;
             if constexpr (LEAN && !SIM && KS_CLAIM_RUNS) {
               // the identical pods that follow land here too (claim_run_cap): placed in one step.  While nothing
               // was pushed back (ident) the queue is NewQueue's order and the run is the popped pod's run length
@@ -903,7 +916,10 @@
                     // there.  The run goes on at the claim's new position p' while every position before p' fails
                     // the quick test (an upper bound, so a certain reject; those claims did not change in this
                     // step).  One that passes stops it: the array is sorted and the next pod takes its own step.
+                    PH_BEGIN(trc);
                     const int cap = inl ? S.template claim_run_cap<true>(c, pod, m) : S.template claim_run_cap<false>(c, pod, m);
+                    SXPH_END(S, trc, SS_RUN_CAP);
+                    PH_BEGIN(tcl);
                     int left = m < cap ? m : cap, K = uni(S.s_okey[jj]);
                     // a segment's pods are credited with the first pod's span, the re-sort's regather and the
                     // quick-scan chunks swapped for the segment's own
@@ -915,7 +931,10 @@
                     while (U(left > 0)) {
                       if (!srt) {
                         PH_BEGIN(tx);
-                        exact += S.sort_claims(nclaims);
+                        int npos;  // the descent is the count just stored at `pos`
+                        const int how = S.sort_claims(nclaims, SORTC ? pos : -1, npos);
+                        exact += how == S.SORT_EXACT;
+                        sortsClosed += how == S.SORT_CLOSED_FORM;
                         slow++;
                         srt = true;
 #ifdef KS_PHASE_STATS
@@ -923,22 +942,33 @@
                           const uint64_t dt = __builtin_amdgcn_s_memtime() - tx;
                           cyc[2] += dt;
                           cyc[5] -= dt;
+                          S.xcyc[SS_CROSS] -= dt;
                         }
 #endif
                         const int64_t sb = S.algbytes - ab0;
                         S.algbytes = ab0;
-                        int fq = -1, np = -1;  // the first position passing the quick test; the claim's position
-                        for (int base = 0; base < nclaims; base += kWave) {
-                          const int j = base + lane();
-                          const uint64_t mq = wballot(j < nclaims && S.claim_quick(j, s, sflags, toltpl, pod));
-                          const uint64_t mc = wballot(j < nclaims && S.s_order[j] == c);
-                          if (fq < 0 && mq) fq = base + ctz64(mq);
-                          if (mc) {
-                            np = base + ctz64(mc);
-                            break;
+                        // the first position passing the quick test; the claim's position: the closed form
+                        // knows it, any other sort leaves it to be looked up in s_order
+                        int fq = -1, np = UI(npos);
+                        if (SORTC && np >= 0) {
+                          for (int base = 0; base < np && fq < 0; base += kWave) {
+                            const int j = base + lane();
+                            const uint64_t mq = wballot(j < np && S.claim_quick(j, s, sflags, toltpl, pod));
+                            if (mq) fq = base + ctz64(mq);
                           }
+                        } else {
+                          for (int base = 0; base < nclaims; base += kWave) {
+                            const int j = base + lane();
+                            const uint64_t mq = wballot(j < nclaims && S.claim_quick(j, s, sflags, toltpl, pod));
+                            const uint64_t mc = wballot(j < nclaims && S.s_order[j] == c);
+                            if (fq < 0 && mq) fq = base + ctz64(mq);
+                            if (mc) {
+                              np = base + ctz64(mc);
+                              break;
+                            }
+                          }
+                          np = UI(np);
                         }
-                        np = UI(np);
                         if (np < 0) {  // unreachable: s_order is a permutation of the claims
                           err = KE_STACK;
                           qlen = 0;
@@ -968,6 +998,7 @@
                       S.s_okey[pos] = K;  // wave-wide store of a uniform value
                       wsync();
                     }
+                    SXPH_END(S, tcl, SS_CROSS);
                   } else {
                     const int cj = uni(S.s_okey[jj]);
                     const int nx = jj + 1 < nclaims ? uni(S.s_okey[jj + 1]) : 0x3fffffff;
@@ -980,6 +1011,7 @@
 #pragma unroll
                     for (int r = 0; r < RM; r++) podk[r] = (int64_t)k * pod[r];
                     int kcnt = 0;
+                    PH_BEGIN(tbk);
                     if (inl) (void)S.template claim_full<true>(c, s, sflags, podk, req, nthr, kcnt);
                     else (void)S.template claim_full<false>(c, s, sflags, podk, req, nthr, kcnt);
                     // (KS_RUN_CROSS: the segments stored the count; the headroom at the final position is the
@@ -987,11 +1019,34 @@
                     const int kk = KS_RUN_CROSS ? 0 : k;
                     srt = inl ? S.template commit_bulk<true>(c, pos, nclaims, kk, podk, req, nthr, kcnt)
                               : S.template commit_bulk<false>(c, pos, nclaims, kk, podk, req, nthr, kcnt);
+                    if constexpr (SORTC) dpos = srt ? -1 : pos;
                     S.algbytes = ab0 + credit;
+                    SXPH_END(S, tbk, SS_BULK);
+                    PH_BEGIN(tlg);
                     if (wi + k <= wn) {  // the run's pods are the window's next lanes
                       const int src = wi + lane() < kWave ? wi + lane() : kWave - 1;
                       S.log_batch(k, __shfl(w.p, src), c, nlog);
-                    } else {  // past the window: the queue holds them (nothing pushed back yet), 64 per load
+                    } else if constexpr (KS_LOG_AHEAD) {
+                      // past the window: the queue holds them (nothing pushed back yet).  Up to four 64-pod chunks
+                      // are loaded before the first is stored: a load waits for the stores issued before it as well
+                      // (vmcnt counts both), so 64 per load is one HBM round trip per chunk.  Lanes at or past k
+                      // read the run's last pod (an index of the run, inside [0, P)); log_batch takes the first n.
+                      for (int b = 0; b < k; b += 4 * kWave) {
+                        int pv[4];
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                          const int e = b + u * kWave + lane();
+                          int pos = qhead + (e < k ? e : k - 1);
+                          pos = pos >= P ? pos - P : pos;
+                          pv[u] = W.queue[pos];
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                          const int left = k - b - u * kWave;
+                          if (left > 0) S.log_batch(left < kWave ? left : kWave, pv[u], c, nlog);
+                        }
+                      }
+                    } else {  // (KS_LOG_AHEAD=0: 64 per load)
                       for (int b = 0; b < k; b += kWave) {
                         int pos = qhead + b + lane();
                         pos = pos >= P ? pos - P : pos;
@@ -999,6 +1054,7 @@
                         S.log_batch(k - b < kWave ? k - b : kWave, pv, c, nlog);
                       }
                     }
+                    SXPH_END(S, tlg, SS_LOG);
                     qhead += k;
                     if (qhead >= P) qhead -= P;
                     qlen -= k;
@@ -1031,6 +1087,7 @@
       nclaims = UI(nclaims);
       hostCtr = UI(hostCtr);
       srt = U(srt);
+      dpos = -1;  // a descent left here is an appended claim's
       if (r < 0) { err = KE_CLAIM_CAP; break; }
       if (r == 1) placed = true;
       if (r == 2) {  // no templates: add() returns a nil error
@@ -1106,12 +1163,15 @@
     W.counters[CT_RUN_CROSS] = cross;
     W.counters[CT_RUN_CROSS_STOPS] = crossStops;
     W.counters[CT_RUN_CROSS_LOST] = crossLost;
+    W.counters[CT_SORT_CLOSED] = sortsClosed;
+    W.counters[CT_TPL_MEMO_HITS] = S.memoHits;
 #ifdef KS_PHASE_STATS
     for (int i = 0; i < 7; i++) W.counters[CT_CYC_POP + i] = (int64_t)cyc[i];
     W.counters[CT_CYC_TOTAL] = (int64_t)(__builtin_amdgcn_s_memtime() - tstart);
     W.counters[CT_CYC_NCOMMIT] = (int64_t)cyc[7];
     for (int i = 0; i < 4; i++) W.counters[CT_CYC_SUB + i] = (int64_t)S.scyc[i];
     for (int i = 0; i < 8; i++) W.counters[CT_FINE + i] = (int64_t)fcyc[i];
+    for (int i = 0; i < 12; i++) W.counters[CT_STEP + i] = (int64_t)S.xcyc[i];
 #endif
   }
   if constexpr (SIM) S.sim_record(P, nclaims, hostCtr, allSched, err, !ident, anyRelaxed);

@@ -19,7 +19,14 @@ st = r.stats
 tot = max(st["cycTotal"], 1)
 print(json.dumps(st))
 for k in ["cycPop", "cycNodes", "cycNodeCommit", "cycSort", "cycQuick", "cycFull", "cycFullRs", "cycFullThr",
-          "cycFullMasks", "cycFullApply", "cycCommit", "cycTemplates"]:
+          "cycFullMasks", "cycFullApply", "cycCommit", "cycTemplates",
+          # the step's sub-phases: inside cycSort, cycCommit and cycTemplates
+          "cycSortFast", "cycSortExact", "cycSortClosed", "cycRunCap", "cycCross", "cycBulk", "cycLog",
+          "cycTplDerive", "cycTplStore", "cycTplMax"]:
     print("%-14s %6.1f%%  %8.1f cyc/pod" % (k, 100.0 * st[k] / tot, st[k] / n))
+closed, exact = st["sortsClosed"], st["sortsExact"]
+print("re-sorts with a descent %d: fast %d exact %d closed %d;  n <= 12: %d, 12 < n < 50: %d, n >= 50: %d;  tplMemoHits %d" % (
+    st["sortsWithDescent"], st["sortsWithDescent"] - exact - closed, exact, closed, st["sortsLe12"], st["sortsLt50"],
+    st["sortsWithDescent"] - st["sortsLe12"] - st["sortsLt50"], st["tplMemoHits"]))
 print("total cyc/pod %.1f  pops %d  sorts %d slow %d  claims %d  solve_kernel_ms %.2f" % (
     tot / n, st["pops"], st["sorts"], st["sortsWithDescent"], st["nclaims"], r.solve_kernel_ms))
