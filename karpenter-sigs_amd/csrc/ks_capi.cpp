@@ -240,6 +240,13 @@ void ks_upload(ks_problem* pb) {
     for (int r = 0; r < h.dims.R; r++)
       tplAlloc[(size_t)i * h.dims.R + r] = t.it_alloc[(size_t)t.tpl_its[(size_t)i] * h.dims.R + r];
   size_t o_tpa = put(tplAlloc.data(), tplAlloc.size() * 8);
+  // the templates' Pareto fronts (the LEAN Solve's run capacity reads these positions only)
+  std::vector<int32_t> frontBeg, frontPos;
+  pareto_fronts(h.dims, t.tpl_it_beg, t.tpl_its, t.it_alloc, frontBeg, frontPos);
+  const int32_t frontTotal = (int32_t)frontPos.size();
+  if (frontPos.empty()) frontPos.push_back(0);
+  size_t o_fb = put(frontBeg.data(), frontBeg.size() * 4);
+  size_t o_fp = put(frontPos.data(), frontPos.size() * 4);
   size_t o_tsp = put(t.tsort_pos.data(), t.tsort_pos.size() * 4);
   size_t o_pr = put(t.pool_rem0.data(), t.pool_rem0.size() * 8);
   size_t o_pm = put(t.pool_mask.data(), t.pool_mask.size() * 4);
@@ -393,6 +400,9 @@ void ks_upload(ks_problem* pb) {
   D.tpl_pool = (const int32_t*)(b + o_tp);
   D.tsort_alloc = (const int64_t*)(b + o_tsa);
   D.tpl_alloc = (const int64_t*)(b + o_tpa);
+  D.tpl_front_beg = (const int32_t*)(b + o_fb);
+  D.tpl_front = (const int32_t*)(b + o_fp);
+  D.frontTotal = frontTotal;
   D.tsort_pos = (const int32_t*)(b + o_tsp);
   D.pool_rem0 = (const int64_t*)(b + o_pr);
   D.pool_mask = (const uint32_t*)(b + o_pm);
@@ -1114,10 +1124,21 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   kv("volSharedPods", nshared); kv("volErrorPods", nverr); kv("injectFailed", nfail);
   kv("volStaticMounts", (long long)(h.tab.pod_vsbeg.empty() ? 0 : h.tab.pod_vsbeg.back()));
   // LDS plans (ks_solve.hip make_plan) at the default and a few reduced budgets
+  // the templates' Pareto fronts (pareto_fronts): positions per template, [] where a template is not pruned
+  std::vector<int32_t> frontBeg, frontPos;
+  pareto_fronts(d, h.tab.tpl_it_beg, h.tab.tpl_its, h.tab.it_alloc, frontBeg, frontPos);
+  o += ",\"runFuse\":" + std::to_string(run_fuse_build()) + ",\"paretoFronts\":[";
+  for (int t = 0; t < d.NTPL; t++) {
+    o += t ? ",[" : "[";
+    for (int i = frontBeg[(size_t)t]; i < frontBeg[(size_t)t + 1]; i++)
+      o += (i > frontBeg[(size_t)t] ? "," : "") + std::to_string(frontPos[(size_t)i]);
+    o += "]";
+  }
+  o += "]";
   o += ",\"plans\":{";
   const size_t budgets[] = {160 * 1024 - 256, 6000, 9000, 14000, 24000, 40000};
   for (size_t i = 0; i < sizeof(budgets) / sizeof(budgets[0]); i++) {
-    Plan pl = make_plan(d, budgets[i]);
+    Plan pl = make_plan(d, budgets[i], false, 0, (int)frontPos.size());
     o += (i ? ",\"" : "\"") + std::to_string(budgets[i]) + "\":{\"KO\":" + std::to_string(pl.KO) +
          ",\"KL\":" + std::to_string(pl.KL) + ",\"talloc\":" + std::to_string(pl.talloc) +
          ",\"tsort\":" + std::to_string(pl.tsort) + ",\"lds\":" + std::to_string(pl.lds) + "}";
@@ -1241,7 +1262,7 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   size_t budget = 160 * 1024 - 256;
   if (reps > 256) budget = std::max<size_t>(24 * 1024, budget * 256 / reps);
   if (opts && opts->lds_budget > 0) budget = std::min<size_t>(budget, (size_t)opts->lds_budget);
-  Plan pl = make_plan(d, budget, false, pb->wideKO);
+  Plan pl = make_plan(d, budget, false, pb->wideKO, pb->dev.frontTotal);
   if (pl.lds > 160 * 1024 || pl.KO < 1)
     throw KsError(KS_ERR_CAPACITY, "solve state does not fit the LDS budget");
   pb->lastKO = pl.KO;
@@ -1309,8 +1330,8 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
     // and solve again
     const int prevKO = pl.KO;
     pb->wideKO++;
-    pl = make_plan(d, budget, false, pb->wideKO);
-    if (pb->wideKO == 1 && pl.KO <= prevKO) pl = make_plan(d, budget, false, pb->wideKO = 2);
+    pl = make_plan(d, budget, false, pb->wideKO, pb->dev.frontTotal);
+    if (pb->wideKO == 1 && pl.KO <= prevKO) pl = make_plan(d, budget, false, pb->wideKO = 2, pb->dev.frontTotal);
     if (pl.lds > 160 * 1024 || pl.KO < 1) break;
     pb->lastKO = pl.KO;
   }
@@ -1378,7 +1399,7 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "runCross", "runCrossStops", "runCrossLost", "sortsClosed", "tplMemoHits",
                                 "cycSortFast", "cycSortExact", "cycSortClosed", "sortsLe12", "sortsLt50",
                                 "cycRunCap", "cycCross", "cycBulk", "cycLog", "cycTplDerive", "cycTplStore",
-                                "cycTplMax"};
+                                "cycTplMax", "runCapFront", "runCapFull", "runCrossClosed", "runMoves"};
   static_assert(sizeof(names) / sizeof(names[0]) == CT_NCOUNTERS, "one name per counter");
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);
   // the launched k_solve instantiation: the last launch's fields, and every launch of this Solve in order

@@ -1596,4 +1596,42 @@ std::vector<std::string> Host::compatErrors(const uint32_t* r, const uint32_t* i
   return out;
 }
 
+void pareto_fronts(const KsDims& dims, const std::vector<int32_t>& tpl_it_beg, const std::vector<int32_t>& tpl_its,
+                   const std::vector<int64_t>& it_alloc, std::vector<int32_t>& beg, std::vector<int32_t>& pos) {
+  const int R = dims.R, NT = dims.NTPL;
+  beg.assign((size_t)NT + 1, 0);
+  pos.clear();
+  for (int t = 0; t < NT; t++) {
+    const int tb = tpl_it_beg[(size_t)t], n = tpl_it_beg[(size_t)t + 1] - tb;
+    auto al = [&](int q) { return &it_alloc[(size_t)tpl_its[(size_t)(tb + q)] * R]; };
+    // Allocatable descending (lexicographic), then position: whatever dominates q stands before q, so q is on the
+    // front iff no front member found so far dominates it (dominance is transitive)
+    std::vector<int> ord((size_t)n);
+    for (int i = 0; i < n; i++) ord[(size_t)i] = i;
+    std::sort(ord.begin(), ord.end(), [&](int a, int b) {
+      const int64_t *x = al(a), *y = al(b);
+      for (int r = 0; r < R; r++)
+        if (x[r] != y[r]) return x[r] > y[r];
+      return a < b;
+    });
+    std::vector<int32_t> front;
+    for (int i = 0; i < n && (int)front.size() <= kFrontMax; i++) {
+      const int64_t* x = al(ord[(size_t)i]);
+      bool dominated = false;
+      for (size_t f = 0; f < front.size() && !dominated; f++) {
+        const int64_t* y = al(front[f]);
+        bool ge = true;
+        for (int r = 0; r < R && ge; r++) ge = y[r] >= x[r];
+        dominated = ge;
+      }
+      if (!dominated) front.push_back(ord[(size_t)i]);
+    }
+    if ((int)front.size() <= kFrontMax) {
+      std::sort(front.begin(), front.end());
+      pos.insert(pos.end(), front.begin(), front.end());
+    }
+    beg[(size_t)t + 1] = (int32_t)pos.size();
+  }
+}
+
 }  // namespace ks

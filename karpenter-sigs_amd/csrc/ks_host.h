@@ -269,6 +269,14 @@ inline bool gtest(const std::vector<uint64_t>& v, size_t row, int gmw, int g) {
   return (v[row * (size_t)gmw + (size_t)(g >> 6)] >> (g & 63)) & 1ull;
 }
 
+// Pareto front of every template's Allocatable vectors, from the tables the kernel reads (it_alloc via tpl_its):
+// position q of a template is dropped when another position's Allocatable is >= q's in each of the R resources
+// (of equal vectors the lowest position stays).  CSR over the templates, positions ascending; a template whose
+// front exceeds kFrontMax positions gets an empty range (not pruned).  Derived at upload, never stored.
+constexpr int kFrontMax = 64;
+void pareto_fronts(const KsDims& dims, const std::vector<int32_t>& tpl_it_beg, const std::vector<int32_t>& tpl_its,
+                   const std::vector<int64_t>& it_alloc, std::vector<int32_t>& beg, std::vector<int32_t>& pos);
+
 struct ArOut;
 struct ArIn;
 void host_save(ArOut& a, Host& h);

@@ -203,6 +203,12 @@ struct KsDev {
   const int32_t KS_G* vol_udrv;    // [NVU] driver of PVC u
   const int32_t KS_G* n_vc0;       // [N][VD] PVCs of driver v mounted on the node (|VolumeUsage.volumes[v]|)
   const int32_t KS_G* n_vlim;      // [N][VD] the node's limit for driver v (INT32_MAX: none)
+  // Pareto front of each template's Allocatable vectors (ks_host.cpp pareto_fronts; the LEAN Solve's claim_run_cap):
+  // the template positions no other position dominates, CSR.  An empty range: the template is not pruned.
+  // (last, so that every other field keeps its kernel-argument offset)
+  const int32_t KS_G* tpl_front_beg;  // [NTPL+1]
+  const int32_t KS_G* tpl_front;      // [frontTotal] template positions, ascending
+  int32_t frontTotal;
 };
 
 enum NodeFlag : int32_t { NF_UNUSABLE = 1 };
@@ -332,7 +338,12 @@ enum Counter {
   CT_TPL_MEMO_HITS,            // LEAN Solve NewNodeClaims that reused the last one's derived state (KS_TPL_MEMO)
   // diagnostic build: the LEAN Solve's step in sub-phases (cycles unless noted)
   CT_STEP,                     // [12], the StepSub slots
-  CT_NCOUNTERS = CT_STEP + 12
+  CT_RUN_CAP_FRONT = CT_STEP + 12,  // LEAN Solve claim_run_cap calls that read the template's Pareto front only (KS_RUN_FRONT)
+  CT_RUN_CAP_FULL,                  // ... and those that scanned every remaining option
+  CT_RUN_CROSS_CLOSED,              // in-run re-sorts (runCross + runCrossStops) that took the closed form
+  CT_RUN_MOVES,                     // moves of a run's claim in the position arrays (KS_RUN_FUSE: one per run, stop
+                                    // and general re-sort; otherwise one per in-run re-sort)
+  CT_NCOUNTERS
 };
 enum StepSub {
   SS_SORT_FAST = 0,  // re-sorts the wave-parallel partialInsertionSort finished (inside CT_CYC_SORT, as the next two)

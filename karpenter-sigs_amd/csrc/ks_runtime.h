@@ -26,7 +26,9 @@ void launch_feasibility_nodes(const KsDev& D, hipStream_t st);
 bool sims_mw_supported(const KsDev& D, const Plan& pl);
 hipError_t launch_sims_split(const KsDev& D, const KsWork* works_dev, int nsims, int nmw, const Plan& pl, hipStream_t st,
                              hipStream_t st2, hipEvent_t fork, hipEvent_t join);
-Plan make_plan(const KsDims& d, size_t budget, bool sim = false, int wideKO = 0);
+int run_fuse_build();  // the KS_RUN_FUSE the LEAN Solve was compiled with (ks_problem_inspect reports it)
+// frontTotal: KsDev::frontTotal, the Pareto-front positions a LEAN Solve keeps in LDS
+Plan make_plan(const KsDims& d, size_t budget, bool sim = false, int wideKO = 0, int frontTotal = 0);
 size_t queue_sort_temp_bytes(int n);
 hipError_t queue_sort(const KsDev& D, uint64_t* keys, int32_t* vals, void* temp, size_t tempBytes, int32_t* out,
                       hipStream_t st);

@@ -49,6 +49,15 @@
 #ifndef KS_RUN_CROSS  // those runs stay on their NodeClaim across the re-sorts inside a step (0: end at each)
 #define KS_RUN_CROSS 1
 #endif
+#ifndef KS_RUN_FRONT  // their capacity from the template's Pareto-maximal instance types (0: from every remaining option)
+#define KS_RUN_FRONT 1
+#endif
+// LEAN Solve: 1 composes a run's closed-form crossings into one deferred move of its claim (0: each moves and
+// regathers).  Measured on C2 at -0.018 ms of 6.85 (-0.077 in an earlier session), under the round's margin of three
+// spreads, and at +0.013 ms of 0.322 on the C1 kernel: off
+#ifndef KS_RUN_FUSE
+#define KS_RUN_FUSE 0
+#endif
 #ifndef KS_SORT_CLOSED  // the claim re-sort's closed form at a single count crossing: 0 off, 1 LEAN Solve, 2 every Solve
 #define KS_SORT_CLOSED 1
 #endif
@@ -608,12 +617,24 @@ struct ClaimSort {
   // choosePivot_func (zsortfunc.go): the wave reads the (up to) nine samples at once, lane t sample t,
   // and the medians run on scalars; same pivot and hint as GoSortT::choosePivot.
   __device__ __forceinline__ int w_choose_pivot(int a, int b, int& hint) const {
+    return w_choose_pivot_at(a, b, hint, [this](int pos) { return s_okey[pos]; });
+  }
+  // ... on the array a run's deferred move stands for (KS_RUN_FUSE): the claim taken from pos0 and put at p with
+  // key K, the entries between one place to the left -- index i in [pos0, p) reads i + 1, p reads K
+  __device__ __forceinline__ int w_choose_pivot_moved(int n, int pos0, int p, int K, int& hint) const {
+    return w_choose_pivot_at(0, n, hint, [this, pos0, p, K](int pos) {
+      const int k = s_okey[pos >= pos0 && pos < p ? pos + 1 : pos];
+      return pos == p ? K : k;
+    });
+  }
+  template <class F>
+  __device__ __forceinline__ int w_choose_pivot_at(int a, int b, int& hint, F keyAt) const {
     const int l = b - a;
     int i = a + l / 4, j = a + l / 4 * 2, k = a + l / 4 * 3, swaps = 0;
     if (l >= 8) {
       const int t = lane() < 9 ? lane() : 0, g = t / 3;
       const int pos = (g == 0 ? i : g == 1 ? j : k) + (t % 3) - 1;
-      const int key = s_okey[pos];
+      const int key = keyAt(pos);
       int ik[9], kk[9];
 #pragma unroll
       for (int u = 0; u < 9; u++) {
@@ -932,10 +953,18 @@ struct Solver : ClaimSort {
   LU32 s_firr;          // [TW+2] feas_masks: irregular positions (exact per-position check)
   // LEAN Solve (KS_TPL_MEMO): what the last NewNodeClaim from a template without a NodePool limit derived, keyed by
   // (template, pod requests): options, thresholds, option count, max Allocatable (try_templates)
-  enum : int { MM_T = 0, MM_CNT, MM_POD = 4 };  // then [R] pod, [R] max (int64), [R] thr, [TW] options
+  enum : int { MM_T = 0, MM_CNT, MM_FOK, MM_POD = 4 };  // then [R] pod, [R] max (int64), [R] thr, [TW] options
   static constexpr bool TPL_MEMO = KS_TPL_MEMO && LEAN && !SIM;
   LU32 s_memo;          // [tpl_memo_words]
   int64_t memoHits = 0;
+  // LEAN Solve (KS_RUN_FRONT): the templates' Pareto fronts (KsDev::tpl_front), and per LDS-resident claim whether
+  // its options held every front member that fitted its first requests (try_templates): bit TPL_FOK of lc.tpl
+  static constexpr bool RUN_FRONT = KS_RUN_FRONT && KS_CLAIM_RUNS && LEAN && !SIM;
+  enum : int { TPL_FOK = 1 << 30 };
+  static __device__ __forceinline__ int tplv(int x) { return RUN_FRONT ? x & ~(int)TPL_FOK : x; }
+  LI32 s_fbeg;          // [NTPL+1]
+  LI32 s_front;         // [frontTotal] template positions
+  mutable int64_t capFront = 0, capFull = 0;  // claim_run_cap calls by path
   LU32 s_rmv;           // SIM: [ceil(N/32)] nodes removed by the simulation (the candidates)
   LU32 s_tch;           // SIM: [ceil(N/32)] nodes whose requests live in a W.n_req slot
   LU32 s_tchr;          // SIM: [ceil(N/32)] nodes whose requirements live in a W.n_rs slot; Solve (d.fnOn): nodes
@@ -1924,7 +1953,7 @@ struct Solver : ClaimSort {
       }
       algbytes += 8 * d.RSW;
     }
-    const int t = uni(v.tpl[c]);
+    const int t = tplv(uni(v.tpl[c]));
 #pragma unroll
     for (int r = 0; r < RM; r++) {
       if (RT == 0 && r >= d.R) break;
@@ -2146,7 +2175,7 @@ struct Solver : ClaimSort {
   template <bool INL>
   __device__ __forceinline__ int claim_run_cap(int c, const int64_t* pod, int M) const {
     const ClaimView<INL>& v = cv<INL>();
-    const int t = uni(v.tpl[c]);
+    const int tw = uni(v.tpl[c]), t = tplv(tw);
     const int tb = s_tbeg[t], nIT = s_tbeg[t + 1] - tb;
     float rq[RM];
     int64_t rc[RM];
@@ -2157,6 +2186,29 @@ struct Solver : ClaimSort {
       rc[r] = v.req[(int64_t)c * R() + r];
     }
     int best = 0;
+    if constexpr (RUN_FRONT && INL) {
+      // The maximum is monotone in the Allocatable vector, so an option another remaining option dominates cannot
+      // win.  A LEAN claim loses options through Fits alone, and whatever fits the dominated option fits the
+      // dominating one: with every fitting front member among the claim's first options (TPL_FOK), each remaining
+      // option has a remaining front member above it, and the maximum over those is the maximum.
+      const int fb = s_fbeg[t], nf = s_fbeg[t + 1] - fb;  // at most kWave (pareto_fronts); 0: not pruned
+      if ((tw & TPL_FOK) && nf > 0) {
+        capFront++;
+        const int q = lane() < nf ? s_front[fb + lane()] : 0;
+        if (lane() < nf && ((v.rem[(int64_t)c * d.TW + (q >> 5)] >> (q & 31)) & 1u)) {
+          int cap = M;
+#pragma unroll
+          for (int r = 0; r < RM; r++) {
+            if (RT == 0 && r >= d.R) break;
+            const int x = run_cap(alloc_pos(tb + q, r) - rc[r], pod[r], rq[r], M);
+            cap = x < cap ? x : cap;
+          }
+          best = cap;
+        }
+        return wred_max(best, (int)0x80000000);
+      }
+    }
+    capFull++;
     for (int q0 = 0; q0 < nIT; q0 += kWave) {
       const int q = q0 + lane();
       if (q < nIT && ((v.rem[(int64_t)c * d.TW + (q >> 5)] >> (q & 31)) & 1u)) {
@@ -2351,6 +2403,19 @@ struct Solver : ClaimSort {
                 thr[r] = k;
               }
               const int cnt = hit ? uni((int)s_memo[MM_CNT]) : popc_words(s_rem, d.TW);
+              // KS_RUN_FRONT: did requirements, offerings or a NodePool limit keep a front member that Fits out
+              // of the options?  (claim_run_cap then scans every option of this claim)
+              bool fok = false;
+              if constexpr (RUN_FRONT) {
+                if (hit) {
+                  fok = uni((int)s_memo[MM_FOK]) != 0;
+                } else {
+                  const int fb = s_fbeg[t], nf = s_fbeg[t + 1] - fb;
+                  const int q = lane() < nf ? s_front[fb + lane()] : 0;
+                  const bool miss = lane() < nf && fits_pos(req, tb + q) && !((s_rem[q >> 5] >> (q & 31)) & 1u);
+                  fok = nf > 0 && wballot(miss) == 0;
+                }
+              }
               XPH_END(ttd1, SS_TPL_DERIVE);
               PH_BEGIN(tts1);
               // wave-wide stores of uniform values (see commit_claim)
@@ -2364,7 +2429,7 @@ struct Solver : ClaimSort {
                 }
               }
               if (inl) {
-                lc.tpl[c] = t;
+                lc.tpl[c] = RUN_FRONT && fok ? t | (int)TPL_FOK : t;
                 lc.cnt[c] = cnt;
               } else {
                 gc.cnt[c] = cnt;
@@ -2407,6 +2472,7 @@ struct Solver : ClaimSort {
                     copy_words(s_memo + MM_POD + 5 * R(), s_rem, d.TW);
                     s_memo[MM_T] = (uint32_t)t;
                     s_memo[MM_CNT] = (uint32_t)cnt;
+                    if constexpr (RUN_FRONT) s_memo[MM_FOK] = fok ? 1u : 0u;
                     wsync();
                   }
                 }
@@ -2534,7 +2600,7 @@ struct Solver : ClaimSort {
     for (int j = tlo + lane(); j <= thi; j += kWave) {
       const int c = s_order[j];
       const bool inl = c < pl.KL;
-      s_ptpl[j] = inl ? lc.tpl[c] : W.c_tpl[c];
+      s_ptpl[j] = inl ? tplv(lc.tpl[c]) : W.c_tpl[c];
       for (int r = 0; r < R(); r++) {
         const int64_t i = (int64_t)c * R() + r;
         s_phead[(int64_t)j * R() + r] = inl ? lc.max[i] - lc.req[i] : gc.max[i] - gc.req[i];
@@ -2548,6 +2614,48 @@ struct Solver : ClaimSort {
     else XPH_END(tsc, SS_SORT_EXACT);
 #endif
     return closed ? SORT_CLOSED_FORM : done ? SORT_FAST : SORT_EXACT;
+  }
+
+  // --- a run's deferred move (KS_RUN_FUSE, ks_solve_body.inc) --------------------------------------
+  // Each closed-form crossing of a run lifts its claim over the block of entries below its count and changes
+  // nothing else, so a run's crossings compose into one shift: the position arrays stay as they are while the
+  // run advances, and the claim's entry (physically at pos0) is moved to its position p with count K once.
+  // The entries after p below K: the first t of them, the array being sorted there (sort_claims' count).
+  __device__ __forceinline__ int run_count_below(int p, int n, int K) const {
+    int t = 0;
+    for (int base = p + 1; base < n; base += 4 * kWave) {
+      uint64_t m[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int q = base + u * kWave + lane();
+        m[u] = wballot(q < n && s_okey[q] < K);
+      }
+      bool end = false;
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        t += end ? 0 : popc64(m[u]);
+        end = end || m[u] != ~0ull;
+      }
+      if (end) break;
+    }
+    return t;
+  }
+  // The move itself, the count, and sort_claims' regather of s_ptpl / s_phead over the positions it changed.
+  __device__ __forceinline__ void run_materialise(int pos0, int p, int K) {
+    pis_move(pos0, p);
+    s_okey[p] = K;  // wave-wide store of a uniform value
+    wsync();
+    if (p == pos0) return;
+    for (int j = pos0 + lane(); j <= p; j += kWave) {
+      const int c = s_order[j];
+      const bool inl = c < pl.KL;
+      s_ptpl[j] = inl ? tplv(lc.tpl[c]) : W.c_tpl[c];
+      for (int r = 0; r < R(); r++) {
+        const int64_t i = (int64_t)c * R() + r;
+        s_phead[(int64_t)j * R() + r] = inl ? lc.max[i] - lc.req[i] : gc.max[i] - gc.req[i];
+      }
+    }
+    wsync();
   }
 
   // --- consolidation decision for this simulation (SIM epilogue) -------------------------------
@@ -2613,7 +2721,7 @@ struct Solver : ClaimSort {
     if (nclaims > 0 && err == KE_OK) {
       const int c = uni(s_order[0]);
       const bool inl = c < pl.KL;
-      tpl = inl ? uni(lc.tpl[c]) : uni(W.c_tpl[c]);
+      tpl = inl ? tplv(uni(lc.tpl[c])) : uni(W.c_tpl[c]);
       host = W.c_host[c];
       const uint32_t KS_G* crs = W.c_rs + (int64_t)c * d.RSW;
       wsync();
@@ -3025,27 +3133,28 @@ hipError_t launch_solve_plain(const KsDev& D, const KsWork* w, int n, const Plan
 // wideKO: a Solve that created more NodeClaims than the default plan holds is re-planned with 64 LDS-resident
 // claims and the rest of the LDS given to claim positions: level 1 keeps the instance-type tables in LDS, level 2
 // (when 1 still holds too few) moves them to HBM.  C3 (844 NodeClaims): 56.0k -> 59.1k pods/s at level 1.
-static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO, bool live);
-Plan make_plan(const KsDims& d, size_t budget, bool sim, int wideKO) {
+static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO, bool live, int frontTotal);
+Plan make_plan(const KsDims& d, size_t budget, bool sim, int wideKO, int frontTotal) {
   // The live node list serves the non-LEAN Solve instantiations with a register window (RT 3 or 4, launch_family):
   // a lean problem runs LEAN whenever its instance-type tables fit in LDS (talloc), so its plan reserves the list
   // only when they do not.
   const bool rt = d.R == 3 || d.R == 4;
-  if (sim || !rt) return make_plan_live(d, budget, sim, wideKO, false);
+  if (sim || !rt) return make_plan_live(d, budget, sim, wideKO, false, frontTotal);
   if (d.lean) {
-    const Plan lean = make_plan_live(d, budget, sim, wideKO, false);
+    const Plan lean = make_plan_live(d, budget, sim, wideKO, false, frontTotal);
     if (lean.talloc) return lean;
   }
-  return make_plan_live(d, budget, sim, wideKO, true);
+  return make_plan_live(d, budget, sim, wideKO, true, frontTotal);
 }
 
-static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO, bool live) {
+static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO, bool live, int frontTotal) {
   auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
   Plan pl{};
   const size_t R = d.R, TW = d.TW, tot = d.totalTplIts;
   const size_t fixed = r16(sizeof(KeyMeta) * d.NK) + r16(4 * (size_t)(d.NTPL + 1)) + r16(8 * (size_t)(d.NPOOL + 1) * R) +
                        2 * r16(4 * (size_t)d.RSW) + 5 * r16(4 * TW + 8) + 16 * 16 + (d.volAny ? 48 : 0) +
                        (KS_TPL_MEMO && !sim && d.lean ? r16(4 * (size_t)tpl_memo_words((int)R, (int)TW)) : 0) +
+                       (KS_RUN_FRONT && KS_CLAIM_RUNS && !sim && d.lean ? r16(4 * (size_t)(d.NTPL + 1)) + r16(4 * (size_t)frontTotal) : 0) +
                        (sim ? 4 * r16(4 * (size_t)((d.N + 31) / 32)) : d.fnOn ? r16(4 * (size_t)((d.N + 31) / 32)) : 0) +
                        (d.G ? r16(4 * (size_t)d.G * TGM_WORDS) + r16(4 * (size_t)d.G) + 2 * r16(4 * (size_t)d.RSW) +
                                   (d.GMW > 1 ? r16(8 * (size_t)GS_N * d.GMW) : 0) +
@@ -3096,6 +3205,8 @@ static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO,
            r16(4 * kl * R) + (pl.tsort ? tsortB : 0) + (pl.talloc ? tallocB : 0);
   return pl;
 }
+
+int run_fuse_build() { return KS_RUN_FUSE; }
 
 void launch_feasibility(const KsDev& D, hipStream_t st) {
   const int rows = D.d.S * D.d.NTPL;

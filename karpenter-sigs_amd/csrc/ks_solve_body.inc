@@ -52,6 +52,9 @@
   constexpr bool MEMO = Solver<RT, TL, SIM, TOPO, LEAN>::TPL_MEMO;
   S.s_memo = (LU32)take(MEMO ? 4 * (size_t)tpl_memo_words(R, d.TW) : 0);
   if constexpr (MEMO) S.s_memo[S.MM_T] = (uint32_t)-1;  // empty (wave-wide store of a uniform value)
+  constexpr bool FRONT = Solver<RT, TL, SIM, TOPO, LEAN>::RUN_FRONT;
+  S.s_fbeg = (LI32)take(FRONT ? 4 * (size_t)(d.NTPL + 1) : 0);
+  S.s_front = (LI32)take(FRONT ? 4 * (size_t)D.frontTotal : 0);
   const int NWN = (d.N + 31) >> 5;
   S.s_rmv = (LU32)take(SIM ? 4 * (size_t)NWN : 0);
   S.s_tch = (LU32)take(SIM ? 4 * (size_t)NWN : 0);
@@ -111,6 +114,10 @@
   for (int i = lane(); i < d.NK * (int)(sizeof(KeyMeta) / 4); i += kWave)
     ((uint32_t KS_L*)s_keys)[i] = ((const uint32_t KS_G*)D.keys)[i];
   for (int i = lane(); i <= d.NTPL; i += kWave) S.s_tbeg[i] = D.tpl_it_beg[i];
+  if constexpr (FRONT) {
+    for (int i = lane(); i <= d.NTPL; i += kWave) S.s_fbeg[i] = D.tpl_front_beg[i];
+    for (int i = lane(); i < D.frontTotal; i += kWave) S.s_front[i] = D.tpl_front[i];
+  }
   for (int i = lane(); i < d.NPOOL * R; i += kWave) S.s_pool[i] = SIM ? W.pool0[i] : D.pool_rem0[i];
   const int P = SIM ? W.P : d.P;
   if (!SIM && d.fnOn)
@@ -286,6 +293,8 @@
   // (a position before the claim's new one passed the quick test), and the refusals after which the pod landed
   // on the run's claim all the same (the only ones that cost a step: any other ends the run anyway)
   int64_t cross = 0, crossStops = 0, crossLost = 0;
+  // ... in-run re-sorts that took the closed form, and moves of a run's claim in the position arrays (KS_RUN_FUSE)
+  int64_t crossClosed = 0, runMoves = 0;
   int stopC = -1;                    // the claim of a continuation just refused
   int64_t sortB = 0, pendSortB = 0;  // this add()'s re-sort bytes; those of a re-sort run for the next add()
   // Every pop either places a pod, relaxes it, or marks it stale; the reference's queue can cycle
@@ -853,6 +862,7 @@
         sortB += S.algbytes - ab;
       }
       PH_END(t2, 2);
+      int stepFF = 0;  // positions of this scan that passed the quick test and failed claim_full
       for (int base = 0; U(base < nclaims && !placed && !simNoClaim); base += kWave) {
         PH_BEGIN(t3);
         const int j = base + lane();
@@ -928,6 +938,125 @@
                     int64_t per = ab0 - abPop;
                     k = 0;
                     credit = 0;
+                    if constexpr (KS_RUN_FUSE && SORTC) {
+                      // KS_RUN_FUSE: the position arrays stay untouched while the run advances.  The claim's entry
+                      // stays at pos0; the array the next add() would see has it at p with count K and the entries
+                      // between one place to the left (Solver::run_materialise makes it so: at a stop, before a
+                      // general re-sort, at the run's end).  A crossing is closed-form under sort_claims' conditions,
+                      // choosePivot's hint read on that array (w_choose_pivot_moved); it lifts the claim over the
+                      // t entries below K.  Only those can newly stand before the claim: the positions before pos0
+                      // failed in this step's scan (re-tested when one passed the quick test and failed claim_full,
+                      // stepFF), the blocks crossed earlier were tested at their crossing.
+                      int pos0 = jj, p = jj;
+                      while (U(left > 0)) {
+                        if (!srt) {
+                          int hint = 0;
+                          if (nclaims >= 50) (void)S.w_choose_pivot_moved(nclaims, pos0, p, K, hint);
+                          if (hint == 1) {
+                            const int t = S.run_count_below(p, nclaims, K);
+                            int fq = -1;
+                            for (int base = 0; stepFF && base < pos0 && fq < 0; base += kWave) {
+                              const int j = base + lane();
+                              const uint64_t mq = wballot(j < pos0 && S.claim_quick(j, s, sflags, toltpl, pod));
+                              if (mq) fq = base + ctz64(mq);
+                            }
+                            for (int base = p + 1; base <= p + t && fq < 0; base += kWave) {
+                              const int j = base + lane();
+                              const uint64_t mq = wballot(j <= p + t && S.claim_quick(j, s, sflags, toltpl, pod));
+                              if (mq) fq = base + ctz64(mq);
+                            }
+                            sortsClosed++;
+                            crossClosed++;
+                            slow++;
+                            srt = true;
+                            const int64_t sb = (int64_t)(t + 1) * (8 + 16 * R);  // sort_claims' regather term
+                            p += t;
+                            if (UI(fq) >= 0) {
+                              runMoves++;
+                              S.run_materialise(pos0, p, K);
+                              pos0 = p;
+                              crossStops++;
+                              stopC = c;
+                              pendSortB = sb;  // the next pod's step: it meets the array sorted
+                              break;
+                            }
+                            cross++;
+                            sorts++;  // (the add() this pod would have entered)
+                            per = span0 + sb + (int64_t)min((p / kWave + 1) * kWave, nclaims) * qbytes;
+                          } else {
+                            // the general re-sort: on the array as it stands, then as without KS_RUN_FUSE
+                            runMoves += p != pos0;
+                            S.run_materialise(pos0, p, K);
+                            PH_BEGIN(tx);
+                            int npos;
+                            const int how = S.sort_claims(nclaims, p, npos);
+                            exact += how == S.SORT_EXACT;
+                            sortsClosed += how == S.SORT_CLOSED_FORM;
+                            crossClosed += how == S.SORT_CLOSED_FORM;
+                            slow++;
+                            srt = true;
+#ifdef KS_PHASE_STATS
+                            {
+                              const uint64_t dt = __builtin_amdgcn_s_memtime() - tx;
+                              cyc[2] += dt;
+                              cyc[5] -= dt;
+                              S.xcyc[SS_CROSS] -= dt;
+                            }
+#endif
+                            const int64_t sb = S.algbytes - ab0;
+                            S.algbytes = ab0;
+                            int fq = -1, np = UI(npos);
+                            if (np >= 0) {
+                              for (int base = 0; base < np && fq < 0; base += kWave) {
+                                const int j = base + lane();
+                                const uint64_t mq = wballot(j < np && S.claim_quick(j, s, sflags, toltpl, pod));
+                                if (mq) fq = base + ctz64(mq);
+                              }
+                            } else {
+                              for (int base = 0; base < nclaims; base += kWave) {
+                                const int j = base + lane();
+                                const uint64_t mq = wballot(j < nclaims && S.claim_quick(j, s, sflags, toltpl, pod));
+                                const uint64_t mc = wballot(j < nclaims && S.s_order[j] == c);
+                                if (fq < 0 && mq) fq = base + ctz64(mq);
+                                if (mc) {
+                                  np = base + ctz64(mc);
+                                  break;
+                                }
+                              }
+                              np = UI(np);
+                            }
+                            if (np < 0) {  // unreachable: s_order is a permutation of the claims
+                              err = KE_STACK;
+                              qlen = 0;
+                              break;
+                            }
+                            pos0 = p = np;
+                            fq = UI(fq);
+                            if (fq >= 0 && fq < p) {
+                              crossStops++;
+                              stopC = c;
+                              pendSortB = sb;
+                              break;
+                            }
+                            cross++;
+                            sorts++;
+                            per = span0 + sb + (int64_t)min((p / kWave + 1) * kWave, nclaims) * qbytes;
+                          }
+                        }
+                        const int nx = p + 1 < nclaims ? uni(S.s_okey[p + 1]) : 0x3fffffff;
+                        int seg = nx - K + 1;
+                        seg = seg < left ? seg : left;
+                        if (seg <= 0) break;  // unreachable: the array is sorted here, so K <= nx
+                        K += seg;
+                        left -= seg;
+                        k += seg;
+                        credit += (int64_t)seg * per;
+                        srt = K <= nx;
+                      }
+                      runMoves += p != pos0;
+                      S.run_materialise(pos0, p, K);
+                      pos = p;
+                    } else
                     while (U(left > 0)) {
                       if (!srt) {
                         PH_BEGIN(tx);
@@ -935,6 +1064,8 @@
                         const int how = S.sort_claims(nclaims, SORTC ? pos : -1, npos);
                         exact += how == S.SORT_EXACT;
                         sortsClosed += how == S.SORT_CLOSED_FORM;
+                        crossClosed += how == S.SORT_CLOSED_FORM;
+                        runMoves++;
                         slow++;
                         srt = true;
 #ifdef KS_PHASE_STATS
@@ -1070,7 +1201,8 @@
           } else {
             // the quick bound was stale: tighten it to the exact max over the current options
             fullFails++;
-            const int t = inl ? uni(S.lc.tpl[c]) : uni(W.c_tpl[c]);
+            stepFF++;
+            const int t = inl ? S.tplv(uni(S.lc.tpl[c])) : uni(W.c_tpl[c]);
             if (inl) S.template recompute_max<true>(c, S.lc.rem + (int64_t)c * d.TW, t, jj);
             else S.template recompute_max<false>(c, S.gc.rem + (int64_t)c * d.TW, t, jj);
           }
@@ -1165,6 +1297,10 @@
     W.counters[CT_RUN_CROSS_LOST] = crossLost;
     W.counters[CT_SORT_CLOSED] = sortsClosed;
     W.counters[CT_TPL_MEMO_HITS] = S.memoHits;
+    W.counters[CT_RUN_CAP_FRONT] = S.capFront;
+    W.counters[CT_RUN_CAP_FULL] = S.capFull;
+    W.counters[CT_RUN_CROSS_CLOSED] = crossClosed;
+    W.counters[CT_RUN_MOVES] = runMoves;
 #ifdef KS_PHASE_STATS
     for (int i = 0; i < 7; i++) W.counters[CT_CYC_POP + i] = (int64_t)cyc[i];
     W.counters[CT_CYC_TOTAL] = (int64_t)(__builtin_amdgcn_s_memtime() - tstart);
