@@ -94,6 +94,36 @@ int ks_problem_inspect(const char* snapshot_json, size_t len, char** dims_json);
  *     [the label keys the instance-type rows decide: those no instance type holds with more than one value]}. */
 int ks_problem_feasibility_rows(ks_problem* p, int which, char** meta_json, uint32_t** words, size_t* n_words);
 
+/* Test and diagnostic entries: what the queue-preparation kernels (ks_queue.hip) read and write.  None of them
+ * runs k_solve.
+ *
+ * ks_problem_queue_inputs: host-only (no device).  The encoded inputs of NewQueue's sort and of the identical-pod
+ * run lengths, so a reference never reads what a kernel wrote.  JSON {"P", "R", "resources": [names in column
+ * order], "resShift": [per resource, the decimal shift of its device unit: 10^shift nano-units], "uids": [per pod], "sortKeys": [per pod, the four components -cpu, -memory, creation second, uid rank
+ * (queue.go:83-112)], "skMin": [4], "skBits": [4], "lean", "dupUids", "hostOrder": null | [the pdqsort-emulated
+ * order the device reads when pods tie on the whole key], "podReq": [per pod, R int64], "podS0": [per pod, the four
+ * words of its first relaxation state: toleration mask low / high, template-toleration set, state flags],
+ * "podFlags": [per pod], "PF_PROVISIONABLE": the provisionable bit of podFlags}.  Free with ks_free. */
+int ks_problem_queue_inputs(const char* snapshot_json, size_t len, char** out_json);
+/* The queue launches a Solve makes before k_solve, on the problem's stream, into buffers of this call filled with
+ * 0xA5 bytes first (a word no kernel stores reads back as 0xA5A5A5A5): the NewQueue radix-sort chain, or the
+ * uploaded host order when pods tie (*device_sorted 0), then -- for a lean problem -- the strict identical-pod run
+ * lengths over that order.  order: P int32 pod indices; run_len: P int32, NULL when the problem is not lean.
+ * Free both with ks_free. */
+int ks_problem_queue_readback(ks_problem* p, int32_t** order, int32_t** run_len, size_t* n, int* device_sorted);
+/* k_rec_headers (the device-side record invariants and header compaction of a consolidation pass) without a
+ * handle.  records: the passes' record batches back to back, pass i holding pass_ns[i] records of RF_HDR + 3 * TW
+ * int32 words; tpl_beg: ntpl + 1 offsets, template t's instance-type list has tpl_beg[t + 1] - tpl_beg[t] <= 32 * TW
+ * entries.  The status words and the block counter are allocated and initialised once, as a handle does it, and
+ * every pass runs over them without re-initialisation.  headers: every pass's pass_ns[i] * RF_HDR words (buffers
+ * filled with 0xA5 bytes before each pass); status: two published words per pass; verdicts_json: per pass, per
+ * record, the message the host's check of the same record throws, "" when it passes (headers and status both NULL:
+ * these verdicts alone, no device).  meta_json: {"RF_HDR",
+ * "RF": {field: index}, "CA": {action: value}, "KE": {kernel error: value}};
+ * n_passes 0 returns the metadata alone (no device needed).  Free the JSON with ks_free. */
+int ks_rec_headers_run(const int32_t* records, const int32_t* pass_ns, int n_passes, int TW, const int32_t* tpl_beg,
+                       int ntpl, int32_t* headers, uint64_t* status, char** verdicts_json, char** meta_json);
+
 /* Solve (scheduler.go:140-189) on the GPU.  Fresh scheduler state every call (a Scheduler is
  * single-use in production, scheduler.go:49 is called per Schedule / per simulation). */
 int ks_solve(ks_problem* p, const ks_solve_opts* opts, ks_results** out);
@@ -289,6 +319,13 @@ int ks_cons_sim_counters(ks_cons* c, int sim, int64_t* out24);
  * re-sorts); n larger than the build's count copies that count. Returns the number copied or a negative
  * KS_ERR_* code. */
 int ks_cons_sim_counters_n(ks_cons* c, int sim, int64_t* out, int n);
+/* Test and diagnostic entry (see ks_problem_queue_readback).  After a ks_cons_run: the plan's per-entry arrays as they stand on the device (no new launch).  words (free with
+ * ks_free): lentries | lentrySim | lpodmap | lrunlen (n int32 each: the pods of every simulation in plan order,
+ * their simulation, every simulation's NewQueue order at its CSR offsets, the identical pods left in the run at
+ * each sorted entry), then rank (P int32: every pod's position in the cluster's NewQueue order).  meta_json: the
+ * document of ks_problem_queue_inputs for the handle's pods plus {"n", "sims", "rbits", "sbits"}.
+ * KS_ERR_ARG before the handle's first run. */
+int ks_cons_queue_readback(ks_cons* c, char** meta_json, int32_t** words, size_t* n_words);
 /* Multi-node probes the last ks_cons_decide / ks_cons_needed_sims ran on this handle's GPU (-1: none resolved).
  * The reference's binary search hands each probe the pod objects the earlier probes relaxed in place
  * (multinodeconsolidation.go:111-114, helpers.go:102-104, preferences.go:60-147): a probe holding such a pod is

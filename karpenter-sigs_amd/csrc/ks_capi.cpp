@@ -205,6 +205,75 @@ struct ks_results {
   std::vector<int64_t> counters;
 };
 
+namespace ks {
+// KsDev::pod_s0: per pod the four words of its first relaxation state (toleration mask, template-toleration set,
+// state flags), which the queue window and the run-length kernels read without going through the state tables.
+std::vector<uint64_t> pod_first_state_words(const Host& h) {
+  const auto& t = h.tab;
+  std::vector<uint64_t> ps0((size_t)std::max(h.dims.P, 1) * 4, 0);
+  for (int p = 0; p < h.dims.P; p++) {
+    const int s0 = t.pod_state0[(size_t)p];
+    ps0[(size_t)p * 4] = t.st_tol[(size_t)s0 * 2];
+    ps0[(size_t)p * 4 + 1] = t.st_tol[(size_t)s0 * 2 + 1];
+    ps0[(size_t)p * 4 + 2] = t.st_toltpl[(size_t)s0];
+    ps0[(size_t)p * 4 + 3] = (uint32_t)t.st_flags[(size_t)s0];
+  }
+  return ps0;
+}
+
+// The document of ks_problem_queue_inputs without its closing brace (ks_cons_queue_readback appends its own fields):
+// the host tables the queue kernels read, as they are uploaded.
+std::string queue_inputs_json(const Host& h) {
+  const KsDims& d = h.dims;
+  const auto& t = h.tab;
+  const size_t P = (size_t)d.P, R = (size_t)d.R;
+  std::string o = "{\"P\":" + std::to_string(d.P) + ",\"R\":" + std::to_string(d.R) + ",\"resources\":[";
+  for (size_t i = 0; i < h.resNames.size(); i++) {
+    if (i) o += ",";
+    ksjson::quote(o, h.resNames[i]);
+  }
+  o += "],\"resShift\":[";
+  for (size_t i = 0; i < h.resShift.size(); i++) o += (i ? "," : "") + std::to_string(h.resShift[i]);
+  o += "],\"uids\":[";
+  for (size_t p = 0; p < P; p++) {
+    if (p) o += ",";
+    ksjson::quote(o, h.pods[p].uid);
+  }
+  o += "]";
+  auto rows = [&](const char* k, size_t n, size_t w, auto&& at) {
+    o += std::string(",\"") + k + "\":[";
+    for (size_t i = 0; i < n; i++) {
+      o += i ? ",[" : "[";
+      for (size_t j = 0; j < w; j++) o += (j ? "," : "") + std::to_string(at(i * w + j));
+      o += "]";
+    }
+    o += "]";
+  };
+  auto ints = [&](const char* k, size_t n, auto&& at) {
+    o += std::string(",\"") + k + "\":[";
+    for (size_t i = 0; i < n; i++) o += (i ? "," : "") + std::to_string(at(i));
+    o += "]";
+  };
+  rows("sortKeys", P, 4, [&](size_t i) { return (long long)t.pod_sortkey[i]; });
+  ints("skMin", 4, [&](size_t i) { return (long long)d.skMin[i]; });
+  ints("skBits", 4, [&](size_t i) { return (long long)d.skBits[i]; });
+  o += ",\"lean\":" + std::to_string(d.lean) + ",\"dupUids\":" + std::to_string(d.dupUids) + ",\"hostOrder\":";
+  if (h.hostQueue.empty()) {
+    o += "null";
+  } else {
+    o += "[";
+    for (size_t i = 0; i < h.hostQueue.size(); i++) o += (i ? "," : "") + std::to_string(h.hostQueue[i]);
+    o += "]";
+  }
+  rows("podReq", P, R, [&](size_t i) { return (long long)t.pod_req[i]; });
+  const std::vector<uint64_t> ps0 = pod_first_state_words(h);
+  rows("podS0", P, 4, [&](size_t i) { return (unsigned long long)ps0[i]; });
+  ints("podFlags", P, [&](size_t i) { return (long long)t.pod_flags[i]; });
+  o += ",\"PF_PROVISIONABLE\":" + std::to_string((int)PF_PROVISIONABLE);
+  return o;
+}
+}  // namespace ks
+
 void ks_upload(ks_problem* pb) {
   Host& h = pb->host;
   auto& t = h.tab;
@@ -259,14 +328,7 @@ void ks_upload(ks_problem* pb) {
   size_t o_st = put(t.st_tol.data(), t.st_tol.size() * 8);
   size_t o_sf = put(t.st_flags.data(), t.st_flags.size() * 4);
   size_t o_stt = put(t.st_toltpl.data(), t.st_toltpl.size() * 8);
-  std::vector<uint64_t> ps0((size_t)std::max(h.dims.P, 1) * 4, 0);
-  for (int p = 0; p < h.dims.P; p++) {
-    const int s0 = t.pod_state0[(size_t)p];
-    ps0[(size_t)p * 4] = t.st_tol[(size_t)s0 * 2];
-    ps0[(size_t)p * 4 + 1] = t.st_tol[(size_t)s0 * 2 + 1];
-    ps0[(size_t)p * 4 + 2] = t.st_toltpl[(size_t)s0];
-    ps0[(size_t)p * 4 + 3] = (uint32_t)t.st_flags[(size_t)s0];
-  }
+  std::vector<uint64_t> ps0 = pod_first_state_words(h);
   size_t o_ps0i = put(ps0.data(), ps0.size() * 8);
   size_t o_na = put(t.n_avail.data(), t.n_avail.size() * 8);
   size_t o_nr = put(t.n_req0.data(), t.n_req0.size() * 8);
@@ -1242,6 +1304,71 @@ int ks_problem_feasibility_rows(ks_problem* pb, int which, char** meta_json, uin
   *meta_json = strdup(o.c_str());
   *words = buf;
   *n_words = n;
+  return KS_OK;
+  API_CATCH
+}
+
+// Host-only: the encoded inputs of the queue kernels (ks_queue.hip), for a reference that reads nothing a kernel wrote.
+int ks_problem_queue_inputs(const char* json, size_t len, char** out) {
+  API_TRY
+  if (!json || !out) throw KsError(KS_ERR_ARG, "null argument");
+  ksjson::Value root = ksjson::Parser(json, len ? len : strlen(json)).parse();
+  Host h;
+  h.build(root);
+  *out = strdup((queue_inputs_json(h) + "}").c_str());
+  return KS_OK;
+  API_CATCH
+}
+
+// Test / diagnostic read-back of the queue launches launch_solve makes before k_solve: queue_sort (or the uploaded
+// host order when pods tie), then the strict run lengths of a lean problem, into buffers of this call filled with
+// 0xA5 bytes first.  The problem's sort workspace is the one a Solve uses; nothing a Solve reads later is written.
+int ks_problem_queue_readback(ks_problem* pb, int32_t** order, int32_t** run_len, size_t* n, int* device_sorted) {
+  API_TRY
+  if (!pb || !order || !run_len || !n || !device_sorted) throw KsError(KS_ERR_ARG, "null argument");
+  const KsDims& d = pb->dev.d;
+  DeviceGuard guard(pb->device, nullptr);
+  const size_t P = (size_t)d.P, np = std::max<size_t>(P, 1), nw = (np + 63) / 64;
+  struct Bufs {
+    int32_t* qorder = nullptr;
+    int32_t* rl = nullptr;
+    uint64_t* words = nullptr;
+    ~Bufs() {
+      for (void* p : {(void*)qorder, (void*)rl, (void*)words})
+        if (p) (void)hipFree(p);
+    }
+  } b;
+  HIPCHK(hipMalloc((void**)&b.qorder, 4 * np));
+  HIPCHK(hipMalloc((void**)&b.rl, 4 * np));
+  HIPCHK(hipMalloc((void**)&b.words, 8 * nw));
+  HIPCHK(hipMemsetAsync(b.qorder, 0xA5, 4 * np, pb->stream));
+  HIPCHK(hipMemsetAsync(b.rl, 0xA5, 4 * np, pb->stream));
+  HIPCHK(hipMemsetAsync(b.words, 0xA5, 8 * nw, pb->stream));
+  HIPCHK(hipMemsetAsync(pb->skeys, 0xA5, 2 * np * sizeof(uint64_t), pb->stream));
+  HIPCHK(hipMemsetAsync(pb->svals, 0xA5, 2 * np * sizeof(int32_t), pb->stream));
+  const int32_t* fixed = pb->hqorder;
+  if (!fixed) HIPCHK(queue_sort(pb->dev, pb->skeys, pb->svals, pb->stemp, pb->stempBytes, b.qorder, pb->stream));
+  const bool lean = d.lean != 0;
+  if (lean)
+    HIPCHK(sim_run_lengths(fixed ? fixed : b.qorder, nullptr, pb->dev.pod_req, pb->dev.pod_s0, pb->dev.pod_flags, d.R,
+                           d.P, b.words, b.rl, pb->stream, true));
+  std::vector<int32_t> ho, hr;
+  dl(ho, fixed ? fixed : b.qorder, P, pb->stream);
+  if (lean) dl(hr, b.rl, P, pb->stream);
+  HIPCHK(hipStreamSynchronize(pb->stream));
+  int32_t* o = (int32_t*)malloc(4 * np);
+  int32_t* r = lean ? (int32_t*)malloc(4 * np) : nullptr;
+  if (!o || (lean && !r)) {
+    free(o);
+    free(r);
+    throw KsError(KS_ERR_INTERNAL, "out of memory");
+  }
+  memcpy(o, ho.data(), 4 * P);
+  if (lean) memcpy(r, hr.data(), 4 * P);
+  *order = o;
+  *run_len = r;
+  *n = P;
+  *device_sorted = fixed ? 0 : 1;
   return KS_OK;
   API_CATCH
 }

@@ -1455,8 +1455,8 @@ struct RecView {
 // agrees with the NodeClaim count (computeConsolidation, consolidation.go:113-194: Delete = none, Replace =
 // exactly one); NewNodeClaims[0]'s options lie in its template's list and number RF_NOPT; filterByPrice's
 // and filterOutSameType's outputs are subsets of their inputs.
-void check_record(const Host& h, const int32_t* r, const std::string& what) {
-  const KsDims& d = h.dims;
+// The check itself needs only the option-word count, the template count and the templates' list lengths.
+void check_record(int TW, int NTPL, const std::function<int(int)>& listLen, const int32_t* r, const std::string& what) {
   if (r[RF_ERROR] != KE_OK)
     throw KsError(r[RF_ERROR] == KE_CLAIM_CAP ? KS_ERR_CAPACITY : KS_ERR_INTERNAL,
                   what + " reported kernel error " + std::to_string(r[RF_ERROR]));
@@ -1466,22 +1466,26 @@ void check_record(const Host& h, const int32_t* r, const std::string& what) {
   if (r[RF_ACTION] == CA_DELETE && r[RF_NCLAIMS] != 0) bad("Delete with NodeClaims");
   if (r[RF_ACTION] == CA_REPLACE && r[RF_NCLAIMS] != 1) bad("Replace without exactly one NodeClaim");
   if (r[RF_NCLAIMS] == 0) return;
-  if (r[RF_TPL] < 0 || r[RF_TPL] >= d.NTPL) bad("template out of range");
-  const int nIT = (int)h.tpls[(size_t)r[RF_TPL]].its.size();
+  if (r[RF_TPL] < 0 || r[RF_TPL] >= NTPL) bad("template out of range");
+  const int nIT = listLen(r[RF_TPL]);
   const uint32_t* o = (const uint32_t*)r + RF_HDR;
   int nopt = 0, nprice = 0, nsame = 0;
-  for (int w = 0; w < d.TW; w++) {
+  for (int w = 0; w < TW; w++) {
     const int lo = w * 32;
     const uint32_t valid = nIT >= lo + 32 ? ~0u : nIT > lo ? (1u << (nIT - lo)) - 1u : 0u;
     if (o[w] & ~valid) bad("options beyond the template's list");
-    if (o[d.TW + w] & ~o[w]) bad("filterByPrice output not a subset of the options");
-    if (o[2 * d.TW + w] & ~o[d.TW + w]) bad("filterOutSameType output not a subset of filterByPrice's");
+    if (o[TW + w] & ~o[w]) bad("filterByPrice output not a subset of the options");
+    if (o[2 * TW + w] & ~o[TW + w]) bad("filterOutSameType output not a subset of filterByPrice's");
     nopt += __builtin_popcount(o[w]);
-    nprice += __builtin_popcount(o[d.TW + w]);
-    nsame += __builtin_popcount(o[2 * d.TW + w]);
+    nprice += __builtin_popcount(o[TW + w]);
+    nsame += __builtin_popcount(o[2 * TW + w]);
   }
   if (nopt != r[RF_NOPT] || nopt == 0) bad("option count");
   if (nprice != r[RF_NPRICE] || nsame != r[RF_NSAME]) bad("price-filter counts");
+}
+
+void check_record(const Host& h, const int32_t* r, const std::string& what) {
+  check_record(h.dims.TW, h.dims.NTPL, [&](int t) { return (int)h.tpls[(size_t)t].its.size(); }, r, what);
 }
 
 // Every gathered record (full records: checked here; headers: k_rec_headers checked them on the device and left
@@ -3326,6 +3330,130 @@ double ks_cons_records_alg_bytes(const ks_cons* c, const void* records, int worl
     sum += (double)(((uint64_t)(uint32_t)x[RF_ALGB_HI] << 32) | (uint32_t)x[RF_ALGB_LO]);
   }
   return sum;
+}
+
+// Test / diagnostic read-back of the plan's per-entry arrays after a run (no launch): what sim_queue_sort and
+// sim_run_lengths left on the device, with the host tables they read.
+int ks_cons_queue_readback(ks_cons* c, char** meta_json, int32_t** words, size_t* n_words) {
+  API_TRY
+  if (!c || !meta_json || !words || !n_words) throw KsError(KS_ERR_ARG, "null argument");
+  if (!c->L.lsorted || c->L.lrank < 0) throw KsError(KS_ERR_ARG, "no ks_cons_run on this handle yet");
+  ks_problem& pb = *c->pb;
+  DeviceGuard guard(pb.device, nullptr);
+  const size_t n = (size_t)c->L.lnent, P = (size_t)pb.host.dims.P, total = 4 * n + P;
+  int32_t* buf = (int32_t*)malloc(std::max<size_t>(total, 1) * 4);
+  if (!buf) throw KsError(KS_ERR_INTERNAL, "out of memory");
+  std::unique_ptr<int32_t, void (*)(void*)> hold(buf, free);
+  HIPCHK(hipStreamSynchronize(pb.stream));
+  if (n) {
+    const int32_t* src[4] = {c->L.lentries, c->L.lentrySim, c->L.lpodmap, c->L.lrunlen};
+    for (int k = 0; k < 4; k++) HIPCHK(hipMemcpy(buf + (size_t)k * n, src[k], 4 * n, hipMemcpyDeviceToHost));
+  }
+  if (P) HIPCHK(hipMemcpy(buf + 4 * n, c->rank, 4 * P, hipMemcpyDeviceToHost));
+  std::string o = queue_inputs_json(pb.host);
+  o += ",\"n\":" + std::to_string(n) + ",\"sims\":" + std::to_string(c->L.lsims.size()) +
+       ",\"rbits\":" + std::to_string(c->L.lrbits) + ",\"sbits\":" + std::to_string(c->L.lsbits) + "}";
+  *meta_json = strdup(o.c_str());
+  *words = hold.release();
+  *n_words = total;
+  return KS_OK;
+  API_CATCH
+}
+
+// k_rec_headers without a handle: the status words and the block counter are set once, as prepare_launch sets
+// L.lst, and every pass runs over them as it finds them.
+int ks_rec_headers_run(const int32_t* records, const int32_t* pass_ns, int n_passes, int TW, const int32_t* tpl_beg,
+                       int ntpl, int32_t* headers, uint64_t* status, char** verdicts_json, char** meta_json) {
+  API_TRY
+  if (meta_json) {
+    std::string m = "{\"RF_HDR\":" + std::to_string((int)RF_HDR) + ",\"RF\":{";
+    const std::pair<const char*, int> rf[] = {{"FLAGS", RF_FLAGS}, {"NCLAIMS", RF_NCLAIMS}, {"HOSTINCR", RF_HOSTINCR},
+                                              {"TPL", RF_TPL}, {"HOST", RF_HOST}, {"ACTION", RF_ACTION},
+                                              {"NOPT", RF_NOPT}, {"NPRICE", RF_NPRICE}, {"NSAME", RF_NSAME},
+                                              {"ERROR", RF_ERROR}, {"ALGB_LO", RF_ALGB_LO}, {"ALGB_HI", RF_ALGB_HI},
+                                              {"CLAIM", RF_CLAIM}};
+    const std::pair<const char*, int> ca[] = {{"NOOP", CA_NOOP}, {"DELETE", CA_DELETE}, {"REPLACE", CA_REPLACE},
+                                              {"ERROR", CA_ERROR}};
+    const std::pair<const char*, int> ke[] = {{"OK", KE_OK}, {"CLAIM_CAP", KE_CLAIM_CAP}, {"ITER_CAP", KE_ITER_CAP},
+                                              {"STACK", KE_STACK}, {"LEAN_EXIT", KE_LEAN_EXIT}};
+    auto obj = [&](const std::pair<const char*, int>* v, size_t cnt) {
+      for (size_t i = 0; i < cnt; i++) m += std::string(i ? ",\"" : "\"") + v[i].first + "\":" + std::to_string(v[i].second);
+    };
+    obj(rf, sizeof(rf) / sizeof(rf[0]));
+    m += "},\"CA\":{";
+    obj(ca, sizeof(ca) / sizeof(ca[0]));
+    m += "},\"KE\":{";
+    obj(ke, sizeof(ke) / sizeof(ke[0]));
+    m += "}}";
+    *meta_json = strdup(m.c_str());
+  }
+  if (n_passes == 0) return KS_OK;
+  const bool hostOnly = !headers && !status;  // the host twin's verdicts alone: no device
+  if (!records || !pass_ns || n_passes < 0 || !tpl_beg || (!hostOnly && (!headers || !status)) || !verdicts_json)
+    throw KsError(KS_ERR_ARG, "null argument");
+  if (TW < 1 || ntpl < 1) throw KsError(KS_ERR_ARG, "TW and ntpl must be positive");
+  for (int t = 0; t < ntpl; t++)
+    if (tpl_beg[t + 1] < tpl_beg[t] || tpl_beg[t + 1] - tpl_beg[t] > 32 * TW)
+      throw KsError(KS_ERR_ARG, "a template's list does not fit TW option words");
+  const size_t recWords = (size_t)RF_HDR + 3 * (size_t)TW;
+  size_t nsMax = 1;
+  for (int i = 0; i < n_passes; i++) {
+    if (pass_ns[i] < 1) throw KsError(KS_ERR_ARG, "a pass needs at least one record");
+    nsMax = std::max(nsMax, (size_t)pass_ns[i]);
+  }
+  struct Bufs {
+    int32_t *rec = nullptr, *hdr = nullptr, *tb = nullptr;
+    unsigned long long *st = nullptr, *sout = nullptr;
+    hipStream_t stream = nullptr;
+    ~Bufs() {
+      for (void* p : {(void*)rec, (void*)hdr, (void*)tb, (void*)st, (void*)sout})
+        if (p) (void)hipFree(p);
+      if (stream) (void)hipStreamDestroy(stream);
+    }
+  } b;
+  if (!hostOnly) {
+    HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    HIPCHK(hipMalloc((void**)&b.rec, 4 * recWords * nsMax));
+    HIPCHK(hipMalloc((void**)&b.hdr, 4 * (size_t)RF_HDR * nsMax));
+    HIPCHK(hipMalloc((void**)&b.tb, 4 * ((size_t)ntpl + 1)));
+    HIPCHK(hipMalloc((void**)&b.st, 32));
+    HIPCHK(hipMalloc((void**)&b.sout, 16));
+    HIPCHK(hipMemcpy(b.tb, tpl_beg, 4 * ((size_t)ntpl + 1), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(b.st, 0xff, 16));  // status words ~0, block counter 0 (prepare_launch)
+    HIPCHK(hipMemset(b.st + 2, 0, 16));
+  }
+  std::string v = "[";
+  const int32_t* src = records;
+  for (int i = 0; i < n_passes; i++) {
+    const size_t ns = (size_t)pass_ns[i];
+    if (!hostOnly) {
+      HIPCHK(hipMemcpyAsync(b.rec, src, 4 * recWords * ns, hipMemcpyHostToDevice, b.stream));
+      HIPCHK(hipMemsetAsync(b.hdr, 0xA5, 4 * (size_t)RF_HDR * nsMax, b.stream));
+      HIPCHK(hipMemsetAsync(b.sout, 0xA5, 16, b.stream));
+      HIPCHK(rec_headers(b.rec, (int)ns, (int)recWords, TW, b.tb, ntpl, b.hdr, b.st, (unsigned*)(b.st + 2), b.sout, b.stream));
+      HIPCHK(hipMemcpyAsync(headers, b.hdr, 4 * (size_t)RF_HDR * ns, hipMemcpyDeviceToHost, b.stream));
+      HIPCHK(hipMemcpyAsync(status + 2 * (size_t)i, b.sout, 16, hipMemcpyDeviceToHost, b.stream));
+      HIPCHK(hipStreamSynchronize(b.stream));
+      headers += (size_t)RF_HDR * ns;
+    }
+    v += i ? ",[" : "[";
+    for (size_t s = 0; s < ns; s++) {
+      std::string msg;
+      try {
+        check_record(TW, ntpl, [&](int t) { return tpl_beg[t + 1] - tpl_beg[t]; }, src + s * recWords, "record");
+      } catch (const KsError& e) {
+        msg = e.what();
+      }
+      if (s) v += ",";
+      ksjson::quote(v, msg);
+    }
+    v += "]";
+    src += recWords * ns;
+  }
+  v += "]";
+  *verdicts_json = strdup(v.c_str());
+  return KS_OK;
+  API_CATCH
 }
 
 }  // extern "C"

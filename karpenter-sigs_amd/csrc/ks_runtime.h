@@ -44,6 +44,11 @@ hipError_t sim_queue_sort(const int32_t* rank, const int32_t* entries, const int
                           int sbits, uint64_t* keys, int32_t* vals, void* temp, size_t tempBytes, int32_t* out,
                           hipStream_t st);
 
+// KsDev::pod_s0 as ks_upload builds it, and the document of ks_problem_queue_inputs without its closing brace
+// (the test and diagnostic read-backs of the queue kernels, ks_capi.cpp)
+std::vector<uint64_t> pod_first_state_words(const Host& h);
+std::string queue_inputs_json(const Host& h);
+
 // One hipMalloc carved into 256-byte aligned arrays.
 struct Arena {
   size_t total = 0;

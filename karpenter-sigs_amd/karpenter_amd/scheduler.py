@@ -84,6 +84,11 @@ def lib():
     l.ks_problem_check_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     l.ks_problem_feasibility_rows.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp),
                                               ctypes.POINTER(ctypes.c_size_t)]
+    l.ks_problem_queue_inputs.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp)]
+    l.ks_problem_queue_readback.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
+                                            ctypes.POINTER(ctypes.c_int)]
+    l.ks_rec_headers_run.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.POINTER(vp),
+                                     ctypes.POINTER(vp)]
     l.ks_cons_save.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
     l.ks_cons_create_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp)]
     l.ks_last_error.restype = ctypes.c_char_p
@@ -122,6 +127,63 @@ def inspect(snapshot):
     out = ctypes.c_void_p()
     _check(lib().ks_problem_inspect(b, len(b), ctypes.byref(out)))
     return json.loads(_take_str(out))
+
+
+def queue_inputs(snapshot):
+    """Host-only (ks_problem_queue_inputs): the encoded inputs of the queue kernels -- per pod the four sort-key
+    components, its request row, first-state words and flags, with skMin / skBits, lean, dupUids and the host
+    order when pods tie -- for a reference that reads nothing a kernel wrote."""
+    b = _encode(snapshot)
+    out = ctypes.c_void_p()
+    _check(lib().ks_problem_queue_inputs(b, len(b), ctypes.byref(out)))
+    return json.loads(_take_str(out))
+
+
+def rec_headers_meta():
+    """RF_* / CA_* / KE_* of the consolidation records, as the library was built (ks_rec_headers_run's metadata;
+    no device)."""
+    meta = ctypes.c_void_p()
+    _check(lib().ks_rec_headers_run(None, None, 0, 0, None, 0, None, None, None, ctypes.byref(meta)))
+    return json.loads(_take_str(meta))
+
+
+def rec_headers_verdicts(records, tw, tpl_beg):
+    """Host-only: per record, the message the host's record check throws ("" when it passes)."""
+    import numpy as np
+
+    flat = np.ascontiguousarray(np.array(records, dtype=np.int32))
+    ns = np.array([len(records)], dtype=np.int32)
+    tb = np.array(tpl_beg, dtype=np.int32)
+    verdicts = ctypes.c_void_p()
+    _check(lib().ks_rec_headers_run(flat.ctypes.data, ns.ctypes.data, 1, tw, tb.ctypes.data, len(tb) - 1, None, None,
+                                    ctypes.byref(verdicts), None))
+    return json.loads(_take_str(verdicts))[0]
+
+
+def rec_headers_run(passes, tw, tpl_beg):
+    """Test / diagnostic driver of k_rec_headers (ks_rec_headers_run): `passes` is a list of record batches, each a
+    list of records of RF_HDR + 3 * tw int32 words; every pass runs over the same device status words and block
+    counter.  Returns per pass (headers as a flat list of ns * RF_HDR ints, [status word 0, status word 1], [the
+    host check's message per record, "" when it passes])."""
+    import numpy as np
+
+    flat = np.ascontiguousarray(np.array([r for batch in passes for r in batch], dtype=np.int32))
+    ns = np.array([len(batch) for batch in passes], dtype=np.int32)
+    tb = np.array(tpl_beg, dtype=np.int32)
+    rf_hdr = rec_headers_meta()["RF_HDR"]
+    assert flat.ndim == 2 and flat.shape[1] == rf_hdr + 3 * tw
+    hdr = np.zeros(int(ns.sum()) * rf_hdr, dtype=np.int32)
+    status = np.zeros(2 * len(passes), dtype=np.uint64)
+    verdicts = ctypes.c_void_p()
+    _check(lib().ks_rec_headers_run(flat.ctypes.data, ns.ctypes.data, len(passes), tw, tb.ctypes.data, len(tb) - 1,
+                                    hdr.ctypes.data, status.ctypes.data, ctypes.byref(verdicts), None))
+    verdicts = json.loads(_take_str(verdicts))
+    out, at = [], 0
+    for i, n in enumerate(ns):
+        out.append(([int(x) for x in hdr[at:at + int(n) * rf_hdr]], [int(status[2 * i]), int(status[2 * i + 1])],
+                    verdicts[i]))
+        at += int(n) * rf_hdr
+    return out
 
 
 def cluster_state(cluster):
@@ -305,6 +367,24 @@ class Scheduler:
             lib().ks_free(words)
         return json.loads(_take_str(meta)), arr
 
+    def queue_readback(self):
+        """Test / diagnostic read-back (ks_problem_queue_readback): the queue launches a Solve makes before k_solve.
+        Returns (order, run lengths or None when the problem is not lean, whether the device sort produced the
+        order), the arrays as lists of P ints."""
+        import numpy as np
+
+        order, rl, n, dev = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_int()
+        _check(lib().ks_problem_queue_readback(self._h, ctypes.byref(order), ctypes.byref(rl), ctypes.byref(n),
+                                               ctypes.byref(dev)))
+        try:
+            o = np.frombuffer(ctypes.string_at(order, n.value * 4), dtype=np.int32).tolist()
+            r = np.frombuffer(ctypes.string_at(rl, n.value * 4), dtype=np.int32).tolist() if rl.value else None
+        finally:
+            lib().ks_free(order)
+            if rl.value:
+                lib().ks_free(rl)
+        return o, r, bool(dev.value)
+
     def solve(self, replicas=1, device=-1, simulation_mode=True, timing_only=False, lds_budget=0):
         """Solve(ctx, pods) with fresh scheduler state; replicas>1 runs that many independent copies
         of the same Solve in one launch (one wavefront each) and returns replica 0's results."""
@@ -403,6 +483,7 @@ def _cons_lib():
                                             ctypes.POINTER(ctypes.c_size_t)]
         l.ks_cons_inspect_disrupt_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp),
                                                      ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        l.ks_cons_queue_readback.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         l._cons_ready = True
     return l
 
@@ -617,6 +698,26 @@ class Consolidator:
         if n < 0:
             _check(n)
         return list(out)[:n]
+
+    def queue_readback(self):
+        """Test / diagnostic read-back after run() (ks_cons_queue_readback): the queue inputs of the handle's pods
+        (as queue_inputs) plus "n", "sims", "rbits", "sbits", and the arrays "lentries", "lentrySim", "lpodmap",
+        "lrunlen" (n ints each) and "rank" (P ints) as they stand on the device."""
+        import numpy as np
+
+        meta, words, nw = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_cons_lib().ks_cons_queue_readback(self._h, ctypes.byref(meta), ctypes.byref(words), ctypes.byref(nw)))
+        try:
+            arr = np.frombuffer(ctypes.string_at(words, nw.value * 4), dtype=np.int32).tolist()
+        finally:
+            lib().ks_free(words)
+        doc = json.loads(_take_str(meta))
+        n = doc["n"]
+        assert len(arr) == 4 * n + doc["P"]
+        for k, name in enumerate(("lentries", "lentrySim", "lpodmap", "lrunlen")):
+            doc[name] = arr[k * n:(k + 1) * n]
+        doc["rank"] = arr[4 * n:]
+        return doc
 
     @property
     def last_reruns(self):
