@@ -111,6 +111,17 @@ int ks_problem_queue_inputs(const char* snapshot_json, size_t len, char** out_js
  * lengths over that order.  order: P int32 pod indices; run_len: P int32, NULL when the problem is not lean.
  * Free both with ks_free. */
 int ks_problem_queue_readback(ks_problem* p, int32_t** order, int32_t** run_len, size_t* n, int* device_sorted);
+/* The re-sort of s.newNodeClaims (scheduler.go:247) as the Solve kernel does it, on arrays of the caller's choosing:
+ * no problem, no Solve.  keys / order: n <= 1024 pod counts and claim ids 0 .. n - 1 per sorted position, sorted in
+ * place.  claim_tpl [n] / claim_head [n][R] (R 3 or 4) are per-claim values from which the kernel fills its two other
+ * position arrays before the sort; ptpl [n] / phead [n][R] receive those arrays as the sort leaves them (equal to
+ * claim_tpl / claim_head of order[j] at every position j).  mode 0: the general path (a claim was appended);
+ * mode 1: the path after a count increment at pos -- keys non-decreasing but for keys[pos] > keys[pos + 1] at most
+ * -- which takes the closed form where the kernel does.  *how (may be NULL): 0 partialInsertionSort finished it,
+ * 1 the exact pdqsort ran, 2 the closed form.  device < 0: the same call computes the expected value on the host
+ * with Go's pdqsort_func (*how 1). */
+int ks_claim_sort_probe(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
+                        const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead, int* how);
 /* k_rec_headers (the device-side record invariants and header compaction of a consolidation pass) without a
  * handle.  records: the passes' record batches back to back, pass i holding pass_ns[i] records of RF_HDR + 3 * TW
  * int32 words; tpl_beg: ntpl + 1 offsets, template t's instance-type list has tpl_beg[t + 1] - tpl_beg[t] <= 32 * TW

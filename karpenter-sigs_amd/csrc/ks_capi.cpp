@@ -14,6 +14,7 @@
 #include "ks_archive.h"
 #include "ks_host.h"
 #include "ks_runtime.h"
+#include "ks_sort_probe.h"
 
 using namespace ks;
 
@@ -1189,7 +1190,8 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   // the templates' Pareto fronts (pareto_fronts): positions per template, [] where a template is not pruned
   std::vector<int32_t> frontBeg, frontPos;
   pareto_fronts(d, h.tab.tpl_it_beg, h.tab.tpl_its, h.tab.it_alloc, frontBeg, frontPos);
-  o += ",\"runFuse\":" + std::to_string(run_fuse_build()) + ",\"paretoFronts\":[";
+  o += ",\"runFuse\":" + std::to_string(run_fuse_build()) + ",\"sortLeaf\":" + std::to_string(sort_leaf_build()) +
+       ",\"closedShift\":" + std::to_string(closed_shift_build()) + ",\"paretoFronts\":[";
   for (int t = 0; t < d.NTPL; t++) {
     o += t ? ",[" : "[";
     for (int i = frontBeg[(size_t)t]; i < frontBeg[(size_t)t + 1]; i++)
@@ -1373,6 +1375,62 @@ int ks_problem_queue_readback(ks_problem* pb, int32_t** order, int32_t** run_len
   API_CATCH
 }
 
+// Test / diagnostic: the claim re-sort on arrays of the caller's choosing (k_claim_sort_probe, ks_solve.hip), or
+// with device < 0 its expected value from Go's pdqsort_func on the host (ks_sort_probe.h).  No problem, no Solve.
+int ks_claim_sort_probe(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
+                        const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead, int* how) {
+  API_TRY
+  if (const char* bad = sort_probe_check(mode, pos, n, R, keys, order, claim_tpl, claim_head, ptpl, phead))
+    throw KsError(KS_ERR_ARG, bad);
+  if (device < 0) {
+    sort_probe_host(n, R, keys, order, claim_tpl, claim_head, ptpl, phead);
+    if (how) *how = 1;
+    return KS_OK;
+  }
+  DeviceGuard guard(device, nullptr);
+  const size_t np = std::max<size_t>((size_t)n, 1);
+  struct Bufs {
+    int32_t *keys = nullptr, *order = nullptr, *ctpl = nullptr, *ptpl = nullptr, *how = nullptr;
+    int64_t *chead = nullptr, *phead = nullptr;
+    hipStream_t stream = nullptr;
+    ~Bufs() {
+      for (void* p : {(void*)keys, (void*)order, (void*)ctpl, (void*)ptpl, (void*)how, (void*)chead, (void*)phead})
+        if (p) (void)hipFree(p);
+      if (stream) (void)hipStreamDestroy(stream);
+    }
+  } b;
+  HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+  HIPCHK(hipMalloc((void**)&b.keys, 4 * np));
+  HIPCHK(hipMalloc((void**)&b.order, 4 * np));
+  HIPCHK(hipMalloc((void**)&b.ctpl, 4 * np));
+  HIPCHK(hipMalloc((void**)&b.ptpl, 4 * np));
+  HIPCHK(hipMalloc((void**)&b.how, 4 * kWave));
+  HIPCHK(hipMalloc((void**)&b.chead, 8 * np * R));
+  HIPCHK(hipMalloc((void**)&b.phead, 8 * np * R));
+  HIPCHK(hipMemsetAsync(b.ptpl, 0xA5, 4 * np, b.stream));
+  HIPCHK(hipMemsetAsync(b.phead, 0xA5, 8 * np * R, b.stream));
+  HIPCHK(hipMemsetAsync(b.how, 0xA5, 4 * kWave, b.stream));
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(b.keys, keys, 4 * (size_t)n, hipMemcpyHostToDevice, b.stream));
+    HIPCHK(hipMemcpyAsync(b.order, order, 4 * (size_t)n, hipMemcpyHostToDevice, b.stream));
+    HIPCHK(hipMemcpyAsync(b.ctpl, claim_tpl, 4 * (size_t)n, hipMemcpyHostToDevice, b.stream));
+    HIPCHK(hipMemcpyAsync(b.chead, claim_head, 8 * (size_t)n * R, hipMemcpyHostToDevice, b.stream));
+  }
+  HIPCHK(claim_sort_probe(b.keys, b.order, n, mode, pos, R, b.ctpl, b.chead, b.ptpl, b.phead, b.how, b.stream));
+  int32_t h = -1;
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(keys, b.keys, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
+    HIPCHK(hipMemcpyAsync(order, b.order, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
+    HIPCHK(hipMemcpyAsync(ptpl, b.ptpl, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
+    HIPCHK(hipMemcpyAsync(phead, b.phead, 8 * (size_t)n * R, hipMemcpyDeviceToHost, b.stream));
+  }
+  HIPCHK(hipMemcpyAsync(&h, b.how, 4, hipMemcpyDeviceToHost, b.stream));
+  HIPCHK(hipStreamSynchronize(b.stream));
+  if (how) *how = h;
+  return KS_OK;
+  API_CATCH
+}
+
 // A problem lives until its last Results is freed too (Results render lazily from it).
 void ks_problem_free(ks_problem* p) {
   if (p && --p->refs == 0) delete p;
@@ -1526,7 +1584,8 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "runCross", "runCrossStops", "runCrossLost", "sortsClosed", "tplMemoHits",
                                 "cycSortFast", "cycSortExact", "cycSortClosed", "sortsLe12", "sortsLt50",
                                 "cycRunCap", "cycCross", "cycBulk", "cycLog", "cycTplDerive", "cycTplStore",
-                                "cycTplMax", "runCapFront", "runCapFull", "runCrossClosed", "runMoves"};
+                                "cycTplMax", "runCapFront", "runCapFull", "runCrossClosed", "runMoves",
+                                "cycSortExactLe12", "cycSortExactLt50", "cycSortExactGe50", "closedShiftDiff"};
   static_assert(sizeof(names) / sizeof(names[0]) == CT_NCOUNTERS, "one name per counter");
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);
   // the launched k_solve instantiation: the last launch's fields, and every launch of this Solve in order

@@ -26,6 +26,7 @@
 namespace ks {
 
 constexpr int kMaxR = 16;         // resource names per problem
+constexpr int kProbeMaxN = 1024;  // positions ks_claim_sort_probe sorts (its arrays fit the default 64 KiB of LDS)
 constexpr int kMaxTpl = 64;       // NodeClaimTemplates (NodePools) per problem (st_toltpl is one 64-bit mask)
 constexpr int kWave = 64;
 
@@ -343,6 +344,9 @@ enum Counter {
   CT_RUN_CROSS_CLOSED,              // in-run re-sorts (runCross + runCrossStops) that took the closed form
   CT_RUN_MOVES,                     // moves of a run's claim in the position arrays (KS_RUN_FUSE: one per run, stop
                                     // and general re-sort; otherwise one per in-run re-sort)
+  CT_CYC_EXACT_BY_N,                // [3] diagnostic build: the exact re-sorts' cycles by size: n <= 12, 12 < n < 50, n >= 50
+  CT_CLOSED_SHIFT_DIFF = CT_CYC_EXACT_BY_N + 3,  // diagnostic build (KS_CLOSED_SHIFT): moved entries whose shifted
+                                                 // s_ptpl / s_phead differ from a regather through the claims (0)
   CT_NCOUNTERS
 };
 enum StepSub {

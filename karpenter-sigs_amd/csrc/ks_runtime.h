@@ -27,6 +27,11 @@ bool sims_mw_supported(const KsDev& D, const Plan& pl);
 hipError_t launch_sims_split(const KsDev& D, const KsWork* works_dev, int nsims, int nmw, const Plan& pl, hipStream_t st,
                              hipStream_t st2, hipEvent_t fork, hipEvent_t join);
 int run_fuse_build();  // the KS_RUN_FUSE the LEAN Solve was compiled with (ks_problem_inspect reports it)
+int sort_leaf_build();     // ... and KS_SORT_LEAF ("sortLeaf"), KS_CLOSED_SHIFT ("closedShift")
+int closed_shift_build();
+// ks_claim_sort_probe's kernel (ks_solve.hip): device pointers, how [64]; n <= kProbeMaxN, R 3 or 4
+hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,
+                            const int64_t* chead, int32_t* ptpl, int64_t* phead, int32_t* how, hipStream_t st);
 // frontTotal: KsDev::frontTotal, the Pareto-front positions a LEAN Solve keeps in LDS
 Plan make_plan(const KsDims& d, size_t budget, bool sim = false, int wideKO = 0, int frontTotal = 0);
 size_t queue_sort_temp_bytes(int n);

@@ -43,6 +43,9 @@
 #ifndef KS_SORT_LANE0  // 1: the claim re-sort's exact pdqsort on lane 0 (the round-2 form)
 #define KS_SORT_LANE0 0
 #endif
+#ifndef KS_SORT_LEAF  // LEAN Solve: the exact re-sort's frames of <= 12 entries by stable rank on the wave (0: insertionSort on lane 0)
+#define KS_SORT_LEAF 1
+#endif
 #ifndef KS_CLAIM_RUNS  // LEAN Solve: runs of identical pods placed on one NodeClaim in one step
 #define KS_CLAIM_RUNS 1
 #endif
@@ -57,6 +60,13 @@
 // spreads, and at +0.013 ms of 0.322 on the C1 kernel: off
 #ifndef KS_RUN_FUSE
 #define KS_RUN_FUSE 0
+#endif
+// LEAN Solve: 1 moves the closed form's block by shifting the four position arrays from registers, its reads
+// issued together (0: pis_move, then a regather of s_ptpl / s_phead through the claims).  Measured on C2 at -0.066 ms
+// of 6.74 (-0.030 before its reads were made unconditional), under the round's margin of three spreads, 0.075 ms
+// (DESIGN §7): off
+#ifndef KS_CLOSED_SHIFT
+#define KS_CLOSED_SHIFT 0
 #endif
 #ifndef KS_SORT_CLOSED  // the claim re-sort's closed form at a single count crossing: 0 off, 1 LEAN Solve, 2 every Solve
 #define KS_SORT_CLOSED 1
@@ -800,9 +810,149 @@ struct ClaimSort {
     }
     wsync();
   }
+  // insertionSort_func on [a, b), b - a <= 12 (KS_SORT_LEAF): it exchanges only a strictly smaller entry with its
+  // left neighbour, so it is a stable sort and its result is the stable-rank permutation.  Lane i holds entry
+  // a + i, reads the others' keys by readlane, counts the entries that sort before its own and stores to its rank:
+  // one LDS read, one write (tests/test_sort_leaf_model.py).
+  __device__ __forceinline__ void w_leaf(int a, int b) {
+    const int len = b - a, l = lane();
+    if (len < 2) return;
+    const bool me = l < len;
+    const int mk = me ? s_okey[a + l] : 0, mv = me ? s_order[a + l] : 0;
+    int rank = 0;
+#pragma unroll 1  // (unrolled, its twelve scalars cost the out-of-line re-sort a callee-saved register: a scratch slot)
+    for (int j = 0; j < len; j++) {
+      const int kj = rdl(mk, j);
+      rank += kj < mk || (kj == mk && j < l) ? 1 : 0;
+    }
+    wsync();
+    if (me) {  // rank < len: a permutation of [a, b)
+      s_okey[a + rank] = mk;
+      s_order[a + rank] = mv;
+    }
+    wsync();
+  }
+  // The closed form of a re-sort whose choosePivot gave the increasing hint, n >= 50, 0 <= pos < n - 1:
+  // the descent is the one a count increment at `pos` left: non-decreasing but key[pos] > key[pos+1].
+  // partialInsertionSort then swaps the pair, finds nothing to move left (key[pos+1] >= key[pos] - 1 >=
+  // key[pos-1]), walks the claim right past the t entries below its key and meets no second descent:
+  // (pos, pos+t] moves one place left, the claim lands at pos + t (tests/test_sort_single_descent.py).
+  // The entries past pos are sorted, so those below the key are the first t of them.
+  // Moves s_okey and s_order and returns t; -1 (nothing moved) when there is no descent at pos.
+  __device__ __forceinline__ int closed_move(int n, int pos) {
+    const int K = uni(s_okey[pos]);
+    if (!(K > uni(s_okey[pos + 1]))) return -1;
+    int t = 0;
+    for (int base = pos + 1; base < n; base += 4 * kWave) {  // four chunks per round trip (pis_descent)
+      uint64_t m[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int q = base + u * kWave + lane();
+        m[u] = wballot(q < n && s_okey[q] < K);
+      }
+      bool end = false;
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        t += end ? 0 : popc64(m[u]);
+        end = end || m[u] != ~0ull;
+      }
+      if (end) break;
+    }
+    pis_move(pos, pos + t);
+    return t;
+  }
+  // The top-level frame of a re-sort of n > 12 entries after a count increment at `pos` (-1: another origin), with
+  // the closed form's move done on all four position arrays (KS_CLOSED_SHIFT).  choosePivot as w_choose_pivot
+  // (`pv`, `hint`); when it gives the increasing hint and the single descent is the one the increment left
+  // (sort_claims), the t entries below the claim's key K -- the first t past pos, the rest being sorted -- move
+  // one place left in s_okey, s_order, ptpl and phead ([.][R]) and the claim's own entries go to pos + t.  Returns
+  // t, or -1 with the arrays untouched.
+  // The reads that do not depend on each other are issued together: the nine samples, K, the next key and the first
+  // 256 keys past pos; then the moved entries of the four arrays, 256 positions per read and write batch, low
+  // positions first (a batch writes one place below what it read: below itself, or onto pos, read before).
+  template <int R>
+  __device__ __forceinline__ int closed_crossing(int n, int pos, LI32 ptpl, LI64 phead, int& hint, int& pv) {
+    const bool cand = pos >= 0 && n >= 50 && pos + 1 < n;
+    const int pc = cand ? pos : 0;  // (n > 12: the reads stay inside the array for any pos)
+    const int K = s_okey[pc], nx = s_okey[pc + 1];
+    int kq[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      // (an unconditional read of a clamped position: a read under `q < n` becomes a branch with its own wait)
+      const int q = pc + 1 + u * kWave + lane(), k = s_okey[q < n ? q : n - 1];
+      kq[u] = q < n ? k : INT32_MAX;
+    }
+    pv = w_choose_pivot(0, n, hint);
+    if (!cand || hint != 1 || !ub(K > nx)) return -1;
+    int t = 0;
+    bool end = false;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const uint64_t m = wballot(kq[u] < K);
+      t += end ? 0 : popc64(m);
+      end = end || m != ~0ull;
+    }
+    for (int base = pos + 1 + 4 * kWave; !end && base < n; base += 4 * kWave) {
+      uint64_t m[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int q = base + u * kWave + lane();
+        m[u] = wballot(q < n && s_okey[q] < K);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        t += end ? 0 : popc64(m[u]);
+        end = end || m[u] != ~0ull;
+      }
+    }
+    const int to = pos + t;  // <= n - 1
+    const int v0 = s_order[pos], tp0 = ptpl[pos];  // uniform addresses: every lane holds the claim's entries
+    int64_t h0[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) h0[r] = phead[(int64_t)pos * R + r];
+    for (int lo = pos + 1; lo <= to; lo += 4 * kWave) {
+      int k[4], v[4], tp[4];
+      int64_t h[4][R];
+      const int nu = (to - lo) / kWave + 1;  // chunks of this batch that hold moved entries (uniform)
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if (u < nu) {  // (reads of clamped positions, as above)
+          const int j = lo + u * kWave + lane(), jj = j <= to ? j : to;
+          k[u] = s_okey[jj];
+          v[u] = s_order[jj];
+          tp[u] = ptpl[jj];
+#pragma unroll
+          for (int r = 0; r < R; r++) h[u][r] = phead[(int64_t)jj * R + r];
+        }
+      }
+      wsync();
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int j = lo + u * kWave + lane();
+        if (u < nu && j <= to) {
+          s_okey[j - 1] = k[u];
+          s_order[j - 1] = v[u];
+          ptpl[j - 1] = tp[u];
+#pragma unroll
+          for (int r = 0; r < R; r++) phead[(int64_t)(j - 1) * R + r] = h[u][r];
+        }
+      }
+      wsync();
+    }
+    s_okey[to] = K;  // wave-wide stores of uniform values (see commit_claim)
+    s_order[to] = v0;
+    ptpl[to] = tp0;
+#pragma unroll
+    for (int r = 0; r < R; r++) phead[(int64_t)to * R + r] = h0[r];
+    wsync();
+    return t;
+  }
   // GoSortExactT::run with the whole wave: frames live one per lane (lane k = stack slot k), the
-  // partitions, reversals and partialInsertionSorts run wave-parallel; insertionSort (<= 12 entries),
-  // heapSort (the depth limit), breakPatterns and choosePivot stay on lane 0.  resumePivot as in run().
+  // partitions, reversals and partialInsertionSorts run wave-parallel, and so do the frames of <= 12 entries
+  // (w_leaf); heapSort (the depth limit) and breakPatterns stay on lane 0.  resumePivot as in run().
+  // LEAF: w_leaf for the frames of <= 12 entries (the LEAN Solve: in the other instantiations, whose re-sort is
+  // inlined, it measured slower on C4 and C5 + topology)
+  template <bool LEAF>
   __device__ void w_pdqsort(int n, int resumePivot) {
     int fa = 0, fb = 0, fl = 0, ff = 0;  // this lane's stack slot: a, b, limit, flags (wb | wp << 1)
     int sp = 0;
@@ -828,6 +978,10 @@ struct ClaimSort {
           resume = false;
           pivot = resumePivot;
         } else {
+          if (KS_SORT_LEAF && LEAF && length <= 12) {
+            w_leaf(a, b);
+            break;
+          }
           if (length <= 12 || limit == 0) {
             if (lane() == 0) {
               GoSortT<LI32> g{s_okey, s_order};
@@ -887,6 +1041,7 @@ struct ClaimSort {
 // for its two call sites; the arguments are the two LDS arrays, not the Solver (a pointer to which would force its
 // state into memory).
 // Returns tlo | (thi + 1) << 15 | done << 30 (positions < 2^14: KsDims::Kcap).
+template <bool LEAF>
 static __device__ __forceinline__ uint32_t claim_sort_general(LI32 okey, LI32 order, int n, int pivot) {
   ClaimSort cs;
   cs.s_order = order;
@@ -901,7 +1056,7 @@ static __device__ __forceinline__ uint32_t claim_sort_general(LI32 okey, LI32 or
       g.run(n, pivot);
     }
 #else
-    cs.w_pdqsort(n, pivot);
+    cs.template w_pdqsort<LEAF>(n, pivot);
 #endif
     tlo = 0;
     thi = n - 1;
@@ -909,7 +1064,7 @@ static __device__ __forceinline__ uint32_t claim_sort_general(LI32 okey, LI32 or
   return (uint32_t)tlo | (uint32_t)(thi + 1) << 15 | (uint32_t)done << 30;
 }
 static __device__ __noinline__ uint32_t claim_sort_general_out(LI32 okey, LI32 order, int n, int pivot) {
-  return claim_sort_general(okey, order, n, pivot);
+  return claim_sort_general<true>(okey, order, n, pivot);
 }
 
 template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN>
@@ -1006,6 +1161,7 @@ struct Solver : ClaimSort {
 #ifdef KS_PHASE_STATS
   mutable uint64_t scyc[4] = {0, 0, 0, 0};  // claim_full sub-phases: requirements, thresholds, masks, apply
   mutable uint64_t xcyc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the step's sub-phases (StepSub)
+  uint64_t ecyc[3] = {0, 0, 0};  // the exact re-sorts' cycles by size (CT_CYC_EXACT_BY_N)
 #endif
 
   __device__ Solver(const KsDev& D_, const KsWork KS_C& W_, const Plan& p_) : D(D_), d(D_.d), W(W_), pl(p_) {}
@@ -2538,6 +2694,9 @@ struct Solver : ClaimSort {
   // (KS_SORT_CLOSED); `npos`: where that claim went (SORT_CLOSED), else -1.
   enum : int { SORT_FAST = 0, SORT_EXACT = 1, SORT_CLOSED_FORM = 2 };
   static constexpr bool SORT_CLOSED = !SIM && (KS_SORT_CLOSED == 2 || (KS_SORT_CLOSED == 1 && LEAN));
+  // (the LEAN Solve alone: its resource count is a compile-time 3 or 4, which the shift keeps in registers)
+  static constexpr bool CLOSED_SHIFT = KS_CLOSED_SHIFT && SORT_CLOSED && LEAN && RT > 0;
+  int64_t shiftDiff = 0;  // diagnostic build: moved entries whose shifted s_ptpl / s_phead differ from a regather
   __device__ __forceinline__ int sort_claims(int n, int pos, int& npos) {
     int tlo = n, thi = -1, pivot = -1;
     bool done = false;
@@ -2546,39 +2705,23 @@ struct Solver : ClaimSort {
     if (n <= 12) XPH_COUNT(SS_SORTS_LE12);
     else if (n < 50) XPH_COUNT(SS_SORTS_LT50);
 #endif
-    bool closed = false;
+    bool closed = false, shifted = false;
     npos = -1;
     if (n > 12) {  // pdqsort_func's top-level frame: choosePivot (reads only), then partialInsertionSort
-      int hint = 0;
-      const int pv = w_choose_pivot(0, n, hint);
+      int hint = 0, pv = 0, ts = -1;
+      if constexpr (CLOSED_SHIFT) ts = closed_crossing<RM>(n, pos, s_ptpl, s_phead, hint, pv);
+      else pv = w_choose_pivot(0, n, hint);
       if (hint == 1) {
         pivot = pv;
-        if constexpr (SORT_CLOSED) {
-          // The descent is the one a count increment at `pos` left: non-decreasing but key[pos] > key[pos+1].
-          // partialInsertionSort then swaps the pair, finds nothing to move left (key[pos+1] >= key[pos] - 1 >=
-          // key[pos-1]), walks the claim right past the t entries below its key and meets no second descent:
-          // (pos, pos+t] moves one place left, the claim lands at pos + t (tests/test_sort_single_descent.py).
-          // The entries past pos are sorted, so those below the key are the first t of them.
+        if (ts >= 0) {  // s_ptpl and s_phead moved with their claims: nothing to regather
+          tlo = pos;
+          thi = npos = pos + ts;
+          done = closed = shifted = true;
+        }
+        if constexpr (SORT_CLOSED && !CLOSED_SHIFT) {
           if (pos >= 0 && n >= 50 && pos + 1 < n) {
-            const int K = uni(s_okey[pos]);
-            if (K > uni(s_okey[pos + 1])) {
-              int t = 0;
-              for (int base = pos + 1; base < n; base += 4 * kWave) {  // four chunks per round trip (pis_descent)
-                uint64_t m[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                  const int q = base + u * kWave + lane();
-                  m[u] = wballot(q < n && s_okey[q] < K);
-                }
-                bool end = false;
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                  t += end ? 0 : popc64(m[u]);
-                  end = end || m[u] != ~0ull;
-                }
-                if (end) break;
-              }
-              pis_move(pos, pos + t);
+            const int t = closed_move(n, pos);
+            if (t >= 0) {
               tlo = pos;
               thi = npos = pos + t;
               done = closed = true;
@@ -2591,27 +2734,51 @@ struct Solver : ClaimSort {
       // (out of line in the LEAN Solve, whose closed form leaves this the rare path; the other instantiations
       // keep it inlined, as measured before)
       const uint32_t g = KS_SORT_OUTLINE && LEAN && !SIM ? claim_sort_general_out(s_okey, s_order, n, pivot)
-                                                          : claim_sort_general(s_okey, s_order, n, pivot);
+                                                          : claim_sort_general<LEAN && !SIM>(s_okey, s_order, n, pivot);
       tlo = (int)(g & 0x7fff);
       thi = (int)(g >> 15 & 0x7fff) - 1;
       done = g >> 30 & 1;
     }
     wsync();
-    for (int j = tlo + lane(); j <= thi; j += kWave) {
-      const int c = s_order[j];
-      const bool inl = c < pl.KL;
-      s_ptpl[j] = inl ? tplv(lc.tpl[c]) : W.c_tpl[c];
-      for (int r = 0; r < R(); r++) {
-        const int64_t i = (int64_t)c * R() + r;
-        s_phead[(int64_t)j * R() + r] = inl ? lc.max[i] - lc.req[i] : gc.max[i] - gc.req[i];
+#ifdef KS_PHASE_STATS
+    if (shifted) {  // the invariant the shift rests on: what it moved is what the regather would have written
+      int diff = 0;
+      for (int j = tlo + lane(); j <= thi; j += kWave) {
+        const int c = s_order[j];
+        const bool inl = c < pl.KL;
+        bool ne = s_ptpl[j] != (inl ? tplv(lc.tpl[c]) : W.c_tpl[c]);
+        for (int r = 0; r < R(); r++) {
+          const int64_t i = (int64_t)c * R() + r;
+          ne = ne || s_phead[(int64_t)j * R() + r] != (inl ? lc.max[i] - lc.req[i] : gc.max[i] - gc.req[i]);
+        }
+        diff += ne ? 1 : 0;
       }
+      shiftDiff += wred_add(diff);
     }
-    wsync();
+#endif
+    if (!shifted) {
+      for (int j = tlo + lane(); j <= thi; j += kWave) {
+        const int c = s_order[j];
+        const bool inl = c < pl.KL;
+        s_ptpl[j] = inl ? tplv(lc.tpl[c]) : W.c_tpl[c];
+        for (int r = 0; r < R(); r++) {
+          const int64_t i = (int64_t)c * R() + r;
+          s_phead[(int64_t)j * R() + r] = inl ? lc.max[i] - lc.req[i] : gc.max[i] - gc.req[i];
+        }
+      }
+      wsync();
+    }
     algbytes += (int64_t)(thi - tlo + 1) * (8 + 16 * R());
 #ifdef KS_PHASE_STATS
     if (closed) XPH_END(tsc, SS_SORT_CLOSED);
     else if (done) XPH_END(tsc, SS_SORT_FAST);
-    else XPH_END(tsc, SS_SORT_EXACT);
+    else {
+      XPH_END(tsc, SS_SORT_EXACT);
+      const uint64_t dt = __builtin_amdgcn_s_memtime() - tsc;
+      ecyc[0] += n <= 12 ? dt : 0;
+      ecyc[1] += n > 12 && n < 50 ? dt : 0;
+      ecyc[2] += n >= 50 ? dt : 0;
+    }
 #endif
     return closed ? SORT_CLOSED_FORM : done ? SORT_FAST : SORT_EXACT;
   }
@@ -3207,6 +3374,86 @@ static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO,
 }
 
 int run_fuse_build() { return KS_RUN_FUSE; }
+int sort_leaf_build() { return KS_SORT_LEAF && !KS_SORT_LANE0; }
+int closed_shift_build() { return KS_CLOSED_SHIFT && KS_SORT_CLOSED; }
+
+// Test / diagnostic kernel (ks_claim_sort_probe): Solver::sort_claims' logic on arrays of the caller's choosing,
+// one wave, no Solve.  keys / order [n] are loaded into LDS with the position arrays ptpl / phead gathered from the
+// claim tables ctpl [n] / chead [n][R] (by claim id); mode 0 sorts as for an appended claim (pos -1), mode 1 as
+// after a count increment at pos, taking the closed form where sort_claims does; all four arrays are written back
+// with how it was done (Solver::SORT_*).
+template <int R>
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_claim_sort_probe(
+    int32_t* keys, int32_t* order, int n, int mode, int pos, const int32_t* ctpl, const int64_t* chead, int32_t* ptpl,
+    int64_t* phead, int32_t* how) {
+  extern __shared__ __attribute__((aligned(16))) char smem_probe[];
+  char KS_L* sp = (char KS_L*)smem_probe;
+  const size_t n4 = (4 * (size_t)n + 15) & ~(size_t)15;
+  ClaimSort cs;
+  LI64 s_phead = (LI64)sp;
+  cs.s_okey = (LI32)(sp + 8 * (size_t)n * R);
+  cs.s_order = (LI32)(sp + 8 * (size_t)n * R + n4);
+  LI32 s_ptpl = (LI32)(sp + 8 * (size_t)n * R + 2 * n4);
+  auto gather = [&](int lo, int hi) {  // sort_claims' regather over positions [lo, hi]
+    for (int j = lo + lane(); j <= hi; j += kWave) {
+      const int c = cs.s_order[j];
+      s_ptpl[j] = ctpl[c];
+      for (int r = 0; r < R; r++) s_phead[(int64_t)j * R + r] = chead[(int64_t)c * R + r];
+    }
+    wsync();
+  };
+  for (int j = lane(); j < n; j += kWave) {
+    cs.s_okey[j] = keys[j];
+    cs.s_order[j] = order[j];
+  }
+  wsync();
+  gather(0, n - 1);
+  if (mode == 0) pos = -1;
+  int tlo = n, thi = -1, pivot = -1, res = 1;
+  bool closed = false;
+  if (n > 12) {
+    int hint = 0, pv = 0, ts = -1;
+    if (KS_CLOSED_SHIFT && KS_SORT_CLOSED) ts = cs.closed_crossing<R>(n, pos, s_ptpl, s_phead, hint, pv);
+    else pv = cs.w_choose_pivot(0, n, hint);
+    if (hint == 1) {
+      pivot = pv;
+      if (ts >= 0) closed = true;  // (nothing to regather)
+      else if (KS_SORT_CLOSED && !KS_CLOSED_SHIFT && pos >= 0 && n >= 50 && pos + 1 < n) {
+        const int t = cs.closed_move(n, pos);
+        if (t >= 0) {
+          closed = true;
+          tlo = pos;
+          thi = pos + t;
+        }
+      }
+    }
+  }
+  if (closed) res = 2;
+  else {
+    const uint32_t g = claim_sort_general<true>(cs.s_okey, cs.s_order, n, pivot);
+    tlo = (int)(g & 0x7fff);
+    thi = (int)(g >> 15 & 0x7fff) - 1;
+    res = g >> 30 & 1 ? 0 : 1;
+  }
+  wsync();
+  gather(tlo, thi);
+  for (int j = lane(); j < n; j += kWave) {
+    keys[j] = cs.s_okey[j];
+    order[j] = cs.s_order[j];
+    ptpl[j] = s_ptpl[j];
+    for (int r = 0; r < R; r++) phead[(int64_t)j * R + r] = s_phead[(int64_t)j * R + r];
+  }
+  how[lane()] = res;  // [kWave], one value
+}
+// n <= kProbeMaxN positions, R 3 or 4 (the LEAN Solve's resource counts); the arrays are device pointers
+hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,
+                            const int64_t* chead, int32_t* ptpl, int64_t* phead, int32_t* how, hipStream_t st) {
+  if (n < 0 || n > kProbeMaxN || (R != 3 && R != 4)) return hipErrorInvalidValue;
+  const size_t lds = 8 * (size_t)n * R + 3 * ((4 * (size_t)n + 15) & ~(size_t)15) + 16;
+  if (R == 3) hipLaunchKernelGGL((k_claim_sort_probe<3>), dim3(1), dim3(kWave), lds, st, keys, order, n, mode, pos, ctpl, chead, ptpl, phead, how);
+  else hipLaunchKernelGGL((k_claim_sort_probe<4>), dim3(1), dim3(kWave), lds, st, keys, order, n, mode, pos, ctpl, chead, ptpl, phead, how);
+  return hipGetLastError();
+}
 
 void launch_feasibility(const KsDev& D, hipStream_t st) {
   const int rows = D.d.S * D.d.NTPL;

@@ -1308,6 +1308,8 @@
     for (int i = 0; i < 4; i++) W.counters[CT_CYC_SUB + i] = (int64_t)S.scyc[i];
     for (int i = 0; i < 8; i++) W.counters[CT_FINE + i] = (int64_t)fcyc[i];
     for (int i = 0; i < 12; i++) W.counters[CT_STEP + i] = (int64_t)S.xcyc[i];
+    for (int i = 0; i < 3; i++) W.counters[CT_CYC_EXACT_BY_N + i] = (int64_t)S.ecyc[i];
+    W.counters[CT_CLOSED_SHIFT_DIFF] = S.shiftDiff;
 #endif
   }
   if constexpr (SIM) S.sim_record(P, nclaims, hostCtr, allSched, err, !ident, anyRelaxed);

@@ -186,6 +186,29 @@ def rec_headers_run(passes, tw, tpl_beg):
     return out
 
 
+def claim_sort_probe(keys, order, claim_tpl, claim_head, mode=0, pos=-1, device=0):
+    """Test / diagnostic (ks_claim_sort_probe): the Solve kernel's claim re-sort on arrays of the caller's choosing,
+    or with device=-1 Go's pdqsort_func on the host.  claim_head is [n][R], R 3 or 4.  Returns (keys, order, ptpl,
+    phead, how) as numpy arrays and an int."""
+    import numpy as np
+
+    k = np.array(keys, dtype=np.int32)
+    o = np.array(order, dtype=np.int32)
+    ct = np.ascontiguousarray(claim_tpl, dtype=np.int32)
+    ch = np.ascontiguousarray(claim_head, dtype=np.int64)
+    n = len(k)
+    assert len(o) == n and len(ct) == n and ch.ndim == 2 and ch.shape[0] == n
+    r = ch.shape[1]
+    pt = np.zeros(n, dtype=np.int32)
+    ph = np.zeros((n, r), dtype=np.int64)
+    how = ctypes.c_int(-1)
+    # (bound here, not in lib(): an earlier commit's library, loaded for an A/B run, lacks the entry)
+    lib().ks_claim_sort_probe.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 6 + [ctypes.POINTER(ctypes.c_int)]
+    _check(lib().ks_claim_sort_probe(device, mode, pos, n, r, k.ctypes.data, o.ctypes.data, ct.ctypes.data,
+                                     ch.ctypes.data, pt.ctypes.data, ph.ctypes.data, ctypes.byref(how)))
+    return k, o, pt, ph, how.value
+
+
 def cluster_state(cluster):
     """Cluster-state accounting (pkg/controllers/state, cluster.go:220-512 + statenode.go:110-333):
     the StateNode accessor values the informers converge to for {"nodeClaims", "nodes", "pods"}, as a
