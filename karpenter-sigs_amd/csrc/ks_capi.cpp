@@ -47,7 +47,7 @@ namespace {
 struct WorkLayout {
   size_t c_tpl, c_cnt, c_thr, c_host, c_req, c_max, c_rs, c_rem, order, n_req, n_rs, queue, qorder, pod_state, last_len,
       log_pod, log_tgt, pod_status, pod_fstate, fail_code, fail_host, pool_rem, counters, n_hp, c_hp, n_vc, vlog, vspec, tg_cnt,
-      tg_ccnt, tg_cpos, fail_rs, log_hg, tg_act, run_len, run_words, total;
+      tg_ccnt, tg_cpos, fail_rs, log_hg, tg_act, run_len, run_words, run_log, total;
   int32_t ccs;  // tg_ccnt row stride
 };
 
@@ -92,6 +92,7 @@ WorkLayout work_layout(const KsDims& d) {
   w.tg_act = a.add(4 * (size_t)std::max(d.G, 1));
   w.run_len = a.add(4 * P);
   w.run_words = a.add(8 * ((P + 63) / 64));
+  w.run_log = a.add(d.lean ? 16 * P : 16);  // (only a LEAN Solve writes records)
   w.total = a.total;
   return w;
 }
@@ -134,6 +135,7 @@ KsWork work_ptrs(char* base, const WorkLayout& w) {
   k.log_hg = (uint64_t*)(base + w.log_hg);
   k.tg_act = (int32_t*)(base + w.tg_act);
   k.run_len = (const int32_t*)(base + w.run_len);
+  k.run_log = (int32_t*)(base + w.run_log);
   k.ccs = w.ccs;
   return k;
 }
@@ -1191,7 +1193,8 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   std::vector<int32_t> frontBeg, frontPos;
   pareto_fronts(d, h.tab.tpl_it_beg, h.tab.tpl_its, h.tab.it_alloc, frontBeg, frontPos);
   o += ",\"runFuse\":" + std::to_string(run_fuse_build()) + ",\"sortLeaf\":" + std::to_string(sort_leaf_build()) +
-       ",\"closedShift\":" + std::to_string(closed_shift_build()) + ",\"paretoFronts\":[";
+       ",\"closedShift\":" + std::to_string(closed_shift_build()) + ",\"tplMasks\":" + std::to_string(tpl_masks_build()) +
+       ",\"logRuns\":" + std::to_string(log_runs_build()) + ",\"paretoFronts\":[";
   for (int t = 0; t < d.NTPL; t++) {
     o += t ? ",[" : "[";
     for (int i = frontBeg[(size_t)t]; i < frontBeg[(size_t)t + 1]; i++)
@@ -1205,7 +1208,8 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
     Plan pl = make_plan(d, budgets[i], false, 0, (int)frontPos.size());
     o += (i ? ",\"" : "\"") + std::to_string(budgets[i]) + "\":{\"KO\":" + std::to_string(pl.KO) +
          ",\"KL\":" + std::to_string(pl.KL) + ",\"talloc\":" + std::to_string(pl.talloc) +
-         ",\"tsort\":" + std::to_string(pl.tsort) + ",\"lds\":" + std::to_string(pl.lds) + "}";
+         ",\"tsort\":" + std::to_string(pl.tsort) + ",\"tmask\":" + std::to_string(pl.tmask) +
+         ",\"tmaskBytes\":" + std::to_string(pl.tmask ? tpl_mask_bytes(d.NTPL, d.TW) : 0) + ",\"lds\":" + std::to_string(pl.lds) + "}";
   }
   o += "}";
   o += ",\"keyNames\":[";
@@ -1468,14 +1472,16 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
     pb->wreps = reps;
   }
   KsWork w0 = work_ptrs((char*)pb->wbuf, wl);
-  hipEvent_t e0, em, e1, ef[4];
+  hipEvent_t e0, em, ep, e1, ef[4];
   HIPCHK(hipEventCreate(&e0));
   HIPCHK(hipEventCreate(&em));
+  HIPCHK(hipEventCreate(&ep));
   HIPCHK(hipEventCreate(&e1));
   for (auto& e : ef) HIPCHK(hipEventCreate(&e));
   // A Solve that outgrows the default plan's NodeClaim capacity runs again with the wide plan; the
   // caller pays both launches, so the reported times are their sums (the re-plan is remembered).
-  float ms = 0, setup = 0, fms = 0, fnms = 0;
+  // (kernel_ms: everything launch_solve launched, k_log_expand included; solve_ms: k_solve alone, em to ep)
+  float ms = 0, setup = 0, post = 0, fms = 0, fnms = 0;
   int feasLaunches = 0, attempts = 0;
   std::vector<Route> routes;
   RouteScope routeScope(&routes);
@@ -1484,12 +1490,15 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
     HIPCHK(hipEventRecord(e0, pb->stream));
     HIPCHK(launch_solve(pb->dev, pb->works_dev, reps, pl, w0.qorder, pb->skeys, pb->svals, pb->stemp,
                         pb->stempBytes, pb->stream, em, pb->hqorder, ef, (int32_t*)w0.run_len,
-                        (uint64_t*)((char*)pb->wbuf + wl.run_words)));
+                        (uint64_t*)((char*)pb->wbuf + wl.run_words), ep));
     HIPCHK(hipEventRecord(e1, pb->stream));
     HIPCHK(hipEventSynchronize(e1));
     float a = 0, b = 0, f = 0;
     HIPCHK(hipEventElapsedTime(&a, e0, e1));
     HIPCHK(hipEventElapsedTime(&b, e0, em));
+    float c = 0;
+    HIPCHK(hipEventElapsedTime(&c, ep, e1));
+    post += c;
     if (pb->dev.d.fmOn) {
       HIPCHK(hipEventElapsedTime(&f, ef[0], ef[1]));
       feasLaunches++;
@@ -1522,6 +1531,7 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(em);
+  (void)hipEventDestroy(ep);
   (void)hipEventDestroy(e1);
   for (auto& e : ef) (void)hipEventDestroy(e);
   ks_results* r;
@@ -1540,7 +1550,7 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   }
   r->routes = routes;
   r->kernel_ms = ms;
-  r->solve_ms = ms - setup;
+  r->solve_ms = ms - setup - post;
   r->feas_ms = fms;
   r->feas_bytes = pb->dev.d.fmOn ? pb->fmBytes * feasLaunches : 0;  // bytes of every launch feas_ms sums
   r->feasn_ms = fnms;
@@ -1585,7 +1595,9 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "cycSortFast", "cycSortExact", "cycSortClosed", "sortsLe12", "sortsLt50",
                                 "cycRunCap", "cycCross", "cycBulk", "cycLog", "cycTplDerive", "cycTplStore",
                                 "cycTplMax", "runCapFront", "runCapFull", "runCrossClosed", "runMoves",
-                                "cycSortExactLe12", "cycSortExactLt50", "cycSortExactGe50", "closedShiftDiff"};
+                                "cycSortExactLe12", "cycSortExactLt50", "cycSortExactGe50", "closedShiftDiff",
+                                "tplMaskFills", "tplMaskHits", "runRecs",
+                                "cycTplCand", "cycTplFeas", "cycTplFilter", "cycTplThr", "cycLogLoad", "cycLogStore"};
   static_assert(sizeof(names) / sizeof(names[0]) == CT_NCOUNTERS, "one name per counter");
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);
   // the launched k_solve instantiation: the last launch's fields, and every launch of this Solve in order

@@ -94,6 +94,7 @@ struct Plan {
   int32_t tcl;     // topology count words [0, tcl) are LDS-resident (>= KsDims::tgSmall)
   int32_t tdl;     // node domain words [0, tdl) of n_tdom are LDS-resident (0 or TK * N)
   int32_t livl;    // a Solve's live node list (LDS words; 0: the scan walks every node)
+  int32_t tmask;   // 1: a LEAN Solve keeps each template's requirement / offering bitsets in LDS (KS_TPL_MASKS)
   uint64_t lds;    // dynamic LDS bytes
 };
 
@@ -317,6 +318,10 @@ struct KsWork {
   int32_t KS_G* n_vslot;    // SIM: [N] n_vc row of a node whose volume usage changed (valid where s_tvol is set)
   int32_t KS_G* vlog;       // [vLogCap][2] (PVC u, node): PF_VSHARED pods' PVCs a placement mounted on a node
   int32_t KS_G* vspec;      // [vLogCap][2] the popped pod's entries of vlog
+  // LEAN Solve (KS_LOG_RUNS): one record (first log entry, first queue position, pods, claim) per run that reached
+  // past the queue window while the queue was still NewQueue's order; k_log_expand writes its log entries.  A record
+  // places at least one pod and a pod is popped once before the first push-back, so P records always suffice.
+  int32_t KS_G* run_log;    // [P][4]
 };
 
 enum Counter {
@@ -347,8 +352,18 @@ enum Counter {
   CT_CYC_EXACT_BY_N,                // [3] diagnostic build: the exact re-sorts' cycles by size: n <= 12, 12 < n < 50, n >= 50
   CT_CLOSED_SHIFT_DIFF = CT_CYC_EXACT_BY_N + 3,  // diagnostic build (KS_CLOSED_SHIFT): moved entries whose shifted
                                                  // s_ptpl / s_phead differ from a regather through the claims (0)
-  CT_NCOUNTERS
+  CT_TPL_MASK_FILLS,  // LEAN Solve: templates whose requirement / offering bitsets were derived and kept (KS_TPL_MASKS)
+  CT_TPL_MASK_HITS,   // ... and NewNodeClaims that missed the memo and read them
+  CT_RUN_RECS,        // LEAN Solve: runs logged as one record for k_log_expand (KS_LOG_RUNS)
+  // diagnostic build: SS_TPL_DERIVE and SS_LOG split further (cycles): the candidate loop with the tpl_rs copy,
+  // feas_masks, the filter loop (Fits and the flags), the thresholds with the front test; a run's queue loads past
+  // the window (waited for), its log_batch calls or its record
+  CT_CYC_SPLIT,
+  CT_CYC_SPLIT_END = CT_CYC_SPLIT + 6,
+  CT_NCOUNTERS = CT_CYC_SPLIT_END
 };
+enum SplitSub { YS_TPL_CAND = 0, YS_TPL_FEAS, YS_TPL_FILTER, YS_TPL_THR, YS_LOG_LOAD, YS_LOG_STORE };
+
 enum StepSub {
   SS_SORT_FAST = 0,  // re-sorts the wave-parallel partialInsertionSort finished (inside CT_CYC_SORT, as the next two)
   SS_SORT_EXACT,     // re-sorts that ran the exact pdqsort

@@ -9,12 +9,13 @@
 
 #include "../../include/karpenter_amd.h"
 #include "ks_host.h"
+#include "ks_tplmask.h"
 
 namespace ks {
 hipError_t launch_solve(const KsDev& D, const KsWork* works_dev, int nrep, const Plan& pl, int32_t* qorder,
                         uint64_t* skeys, int32_t* svals, void* stemp, size_t stempBytes, hipStream_t st,
                         hipEvent_t mid, const int32_t* fixed_order = nullptr, hipEvent_t* feas = nullptr,
-                        int32_t* run_len = nullptr, uint64_t* run_words = nullptr);
+                        int32_t* run_len = nullptr, uint64_t* run_words = nullptr, hipEvent_t post = nullptr);
 hipError_t launch_sims(const KsDev& D, const KsWork* works_dev, int nsims, const Plan& pl, hipStream_t st);
 // The topology simulations' kernel alone, and the feasibility launches launch_sims makes before it (a two-phase
 // consolidation plan, ks_cons.cpp run_sims).
@@ -29,6 +30,8 @@ hipError_t launch_sims_split(const KsDev& D, const KsWork* works_dev, int nsims,
 int run_fuse_build();  // the KS_RUN_FUSE the LEAN Solve was compiled with (ks_problem_inspect reports it)
 int sort_leaf_build();     // ... and KS_SORT_LEAF ("sortLeaf"), KS_CLOSED_SHIFT ("closedShift")
 int closed_shift_build();
+int tpl_masks_build();     // KS_TPL_MASKS ("tplMasks"), KS_LOG_RUNS ("logRuns")
+int log_runs_build();
 // ks_claim_sort_probe's kernel (ks_solve.hip): device pointers, how [64]; n <= kProbeMaxN, R 3 or 4
 hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,
                             const int64_t* chead, int32_t* ptpl, int64_t* phead, int32_t* how, hipStream_t st);

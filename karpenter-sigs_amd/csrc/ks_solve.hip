@@ -82,10 +82,23 @@
 #ifndef KS_LOG_AHEAD
 #define KS_LOG_AHEAD 0
 #endif
+// LEAN Solve: 1 lets a NewNodeClaim that misses the memo read its template's requirement-compatible / has-offering
+// bitsets from LDS, kept by the template's first derivation in this Solve (0: derives them again).  Measured on C2 at
+// -0.154 and -0.125 ms of 6.50 in two sessions, all eight runs faster, under the sessions' margins of three spreads
+// (0.231 and 0.147 ms): off
+#ifndef KS_TPL_MASKS
+#define KS_TPL_MASKS 0
+#endif
+// LEAN Solve: a run past the queue window, while the queue is still NewQueue's order, logs one record and
+// k_log_expand writes its per-pod entries after the Solve (0: the wave reads the pods back, 64 per load)
+#ifndef KS_LOG_RUNS
+#define KS_LOG_RUNS 1
+#endif
 
 #include "ks_gosort.h"
 #include "ks_problem.h"
 #include "ks_reqset.h"
+#include "ks_tplmask.h"
 
 namespace ks {
 
@@ -226,6 +239,9 @@ __device__ __forceinline__ void lds_copy(T KS_L* dst, const T KS_G* src, int n) 
 #define XPH_END(v, slot) xcyc[slot] += __builtin_amdgcn_s_memtime() - v  // the step's sub-phases (Solver member, CT_STEP)
 #define SXPH_END(o, v, slot) o.xcyc[slot] += __builtin_amdgcn_s_memtime() - v  // (from k_solve)
 #define XPH_COUNT(slot) xcyc[slot] += 1
+#define YPH_END(v, slot) ycyc[slot] += __builtin_amdgcn_s_memtime() - v  // SS_TPL_DERIVE / SS_LOG split (Solver member, CT_CYC_SPLIT)
+#define SYPH_END(o, v, slot) o.ycyc[slot] += __builtin_amdgcn_s_memtime() - v  // (from k_solve)
+#define PH_WAIT_LOADS() __builtin_amdgcn_s_waitcnt(0x0f70)  // vmcnt(0): a stamp after it has waited for the loads
 #else
 #define PH_BEGIN(v)
 #define PH_END(v, slot)
@@ -235,6 +251,9 @@ __device__ __forceinline__ void lds_copy(T KS_L* dst, const T KS_G* src, int n) 
 #define XPH_END(v, slot)
 #define SXPH_END(o, v, slot)
 #define XPH_COUNT(slot)
+#define YPH_END(v, slot)
+#define SYPH_END(o, v, slot)
+#define PH_WAIT_LOADS()
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -267,6 +286,29 @@ __global__ void k_init(KsDev D, const KsWork* works, int nrep, const int32_t* qo
     }
     for (int64_t i = gtid; i < d.NU; i += gsz) W.last_len[i] = 0;
     for (int64_t i = gtid; i < CT_NCOUNTERS; i += gsz) W.counters[i] = 0;
+  }
+}
+
+// KS_LOG_RUNS: the commit-log entries of the run records a LEAN Solve left (KsWork::run_log, Solver::log_run_record),
+// written after it by the whole GPU: entry nlog + e of a record (nlog, qhead, k, c) is pod qorder[qhead + e] on claim
+// c.  A record is only written while the queue is NewQueue's order, so the pods are read from that order itself
+// (k_init's source): a push-back later in the Solve may reuse the ring slots W.queue held them in.  The record count
+// is read here, not on the host; k_solve stored none of these entries, so the two kernels' writes are disjoint.
+__global__ __launch_bounds__(256) void k_log_expand(const KsWork* works, int nrep, const int32_t* qorder, int P) {
+  for (int rep = blockIdx.y; rep < nrep; rep += gridDim.y) {
+    const KsWork W = works[rep];
+    const int64_t n = W.counters[CT_RUN_RECS];
+    const int nrec = n < 0 ? 0 : n > P ? P : (int)n;  // (at most P records: KsWork::run_log)
+    for (int r = blockIdx.x; r < nrec; r += gridDim.x) {
+      const int nlog = W.run_log[4 * r], qh = W.run_log[4 * r + 1], k = W.run_log[4 * r + 2], c = W.run_log[4 * r + 3];
+      if (nlog < 0 || qh < 0 || qh >= P || k <= 0 || k > P - nlog) continue;  // (never: the entries lie inside [0, P))
+      for (int e = threadIdx.x; e < k; e += blockDim.x) {
+        int q = qh + e;
+        q = q >= P ? q - P : q;
+        W.log_pod[nlog + e] = qorder[q];
+        W.log_tgt[nlog + e] = c;
+      }
+    }
   }
 }
 
@@ -1112,6 +1154,13 @@ struct Solver : ClaimSort {
   static constexpr bool TPL_MEMO = KS_TPL_MEMO && LEAN && !SIM;
   LU32 s_memo;          // [tpl_memo_words]
   int64_t memoHits = 0;
+  // LEAN Solve (KS_TPL_MASKS, when the plan holds the table: pl.tmask): per template without a NodePool limit, what
+  // filterInstanceTypesByRequirements' requirement and offering tests give for every position -- a function of the
+  // template alone here (try_templates).  Row t: [TW] Intersects, [TW] hasOffering; s_tmv[t]: the row is filled.
+  static constexpr bool TPL_MASKS = KS_TPL_MASKS && LEAN && !SIM;
+  LU32 s_tmask;         // [NTPL][2 * TW]
+  LU32 s_tmv;           // [NTPL]
+  int64_t maskFills = 0, maskHits = 0;
   // LEAN Solve (KS_RUN_FRONT): the templates' Pareto fronts (KsDev::tpl_front), and per LDS-resident claim whether
   // its options held every front member that fitted its first requests (try_templates): bit TPL_FOK of lc.tpl
   static constexpr bool RUN_FRONT = KS_RUN_FRONT && KS_CLAIM_RUNS && LEAN && !SIM;
@@ -1162,6 +1211,7 @@ struct Solver : ClaimSort {
   mutable uint64_t scyc[4] = {0, 0, 0, 0};  // claim_full sub-phases: requirements, thresholds, masks, apply
   mutable uint64_t xcyc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the step's sub-phases (StepSub)
   uint64_t ecyc[3] = {0, 0, 0};  // the exact re-sorts' cycles by size (CT_CYC_EXACT_BY_N)
+  mutable uint64_t ycyc[6] = {0, 0, 0, 0, 0, 0};  // SS_TPL_DERIVE and SS_LOG split (SplitSub)
 #endif
 
   __device__ Solver(const KsDev& D_, const KsWork KS_C& W_, const Plan& p_) : D(D_), d(D_.d), W(W_), pl(p_) {}
@@ -1205,6 +1255,12 @@ struct Solver : ClaimSort {
   // buffered, then one coalesced store.  Per-pod global stores would make the next global load wait
   // for their write acknowledgements (vmcnt counts stores on gfx9).
   int lg_p = 0, lg_t = 0;
+  // LEAN Solve (KS_LOG_RUNS): entries of run records belong to k_log_expand.  lg_lo: the buffered block's lanes
+  // before it were stored already (flushed ahead of a record) or are a record's; every block store is masked to
+  // the lanes from it on, so this kernel and k_log_expand write disjoint entries.
+  static constexpr bool LOG_RUNS = KS_LOG_RUNS && KS_CLAIM_RUNS && LEAN && !SIM;
+  int lg_lo = 0;
+  int runRecs = 0;
   // (A simulation's placements are never read back -- the host reads its record -- so SIM only counts them.)
   __device__ __forceinline__ void log_commit(int p, int tgt, int& nlog) {
     if constexpr (SIM) {
@@ -1217,8 +1273,11 @@ struct Solver : ClaimSort {
     }
     nlog++;
     if ((nlog & (kWave - 1)) == 0) {
-      W.log_pod[nlog - kWave + lane()] = lg_p;
-      W.log_tgt[nlog - kWave + lane()] = lg_t;
+      if (!LOG_RUNS || lane() >= lg_lo) {
+        W.log_pod[nlog - kWave + lane()] = lg_p;
+        W.log_tgt[nlog - kWave + lane()] = lg_t;
+      }
+      if constexpr (LOG_RUNS) lg_lo = 0;
     }
   }
   // Commit-log entries for `n` (<= 64) placements at once: lane t holds entry nlog + t (pod, target).
@@ -1236,8 +1295,11 @@ struct Solver : ClaimSort {
       lg_t = tv;
     }
     if (b0 + n >= kWave) {  // the buffered block is complete: store it, then buffer the wrapped entries
-      W.log_pod[nlog - b0 + lane()] = lg_p;
-      W.log_tgt[nlog - b0 + lane()] = lg_t;
+      if (!LOG_RUNS || lane() >= lg_lo) {
+        W.log_pod[nlog - b0 + lane()] = lg_p;
+        W.log_tgt[nlog - b0 + lane()] = lg_t;
+      }
+      if constexpr (LOG_RUNS) lg_lo = 0;
       if (mine && lane() < b0) {
         lg_p = pv;
         lg_t = tv;
@@ -1248,10 +1310,20 @@ struct Solver : ClaimSort {
   __device__ __forceinline__ void log_flush(int nlog) {
     if constexpr (SIM) return;
     const int k = nlog & (kWave - 1);
-    if (lane() < k) {
+    if (lane() < k && (!LOG_RUNS || lane() >= lg_lo)) {
       W.log_pod[nlog - k + lane()] = lg_p;
       W.log_tgt[nlog - k + lane()] = lg_t;
     }
+  }
+  // A run of k pods from queue position qhead on claim c, the queue being NewQueue's order: one record.  The
+  // buffered entries before it are stored first, so that everything from nlog to nlog + k is k_log_expand's.
+  __device__ __forceinline__ void log_run_record(int k, int qhead, int c, int& nlog) {
+    log_flush(nlog);
+    if (lane() < 4)
+      W.run_log[4 * runRecs + lane()] = lane() == 0 ? nlog : lane() == 1 ? qhead : lane() == 2 ? k : c;
+    runRecs++;
+    nlog += k;
+    lg_lo = nlog & (kWave - 1);
   }
   template <class PR>
   __device__ __forceinline__ bool has_offering(int it, PR rs) const {  // nodeclaim.go:270-278
@@ -2438,9 +2510,22 @@ struct Solver : ClaimSort {
           hit = ub(hit);
         }
       }
+      // KS_TPL_MASKS: under the same conditions the requirement and offering tests of every position are a function
+      // of t alone -- every position is a candidate, the requirements are tpl_rs[t] -- and only Fits reads the pod.
+      // The first derivation of t in this Solve keeps both bitsets (irregular positions resolved exactly); a later
+      // miss reads them: no candidate loop, no feas_masks, no per-position requirement / offering test.  The three
+      // booleans per position are the same, so the options, the failure flags and everything after are too.
+      bool mk = false, mfill = false;
+      if constexpr (TPL_MASKS) {
+        if (pl.tmask && pool < 0 && !d.fmOn && !hit) {
+          mk = uni((int)s_tmv[t]) != 0;
+          mfill = !mk;
+        }
+      }
+      const LU32 tm_ic = TPL_MASKS ? s_tmask + (int64_t)t * 2 * d.TW : s_tmask, tm_of = TPL_MASKS ? tm_ic + d.TW : s_tmask;
       // filterByRemainingResources (scheduler.go:364-383)
       uint64_t anyCand = 0;
-      for (int base = 0; base < (hit ? 0 : nIT); base += kWave) {
+      for (int base = 0; base < (hit || mk ? 0 : nIT); base += kWave) {
         const int pos = base + lane();
         bool ok = pos < nIT;
         if (ok && pool >= 0) {
@@ -2454,6 +2539,7 @@ struct Solver : ClaimSort {
         anyCand |= m;
       }
       wsync();
+      YPH_END(ttd, YS_TPL_CAND);
       if (pool >= 0 && anyCand == 0) {
         code = FC_LIMITS;
       } else {
@@ -2461,8 +2547,10 @@ struct Solver : ClaimSort {
         if (!((toltpl >> t) & 1ull)) {
           code = FC_TAINTS;
         } else {
+          PH_BEGIN(tyc);
           copy_words(s_rs, D.tpl_rs + (int64_t)t * d.RSW, d.RSW);
           wsync();
+          YPH_END(tyc, YS_TPL_CAND);
           bool ok = true;
           if (keys(sflags)) {
             ok = rs_compatible(L, s_rs, s_pin, d.allowWK);
@@ -2496,15 +2584,21 @@ struct Solver : ClaimSort {
             if (hit) {  // the memo's options
               copy_words(s_rem, s_memo + MM_POD + 5 * R(), d.TW);
               any = 1;
-            } else {
+            } else if (!mk) {
+              PH_BEGIN(tyf);
               feas_masks(s_rs, t, fm_row(s, t));
+              YPH_END(tyf, YS_TPL_FEAS);
             }
+            PH_BEGIN(tyl);
             for (int base = 0; base < (hit ? 0 : nIT); base += kWave) {
               const int pos = base + lane();
-              const bool in = pos < nIT && ((s_cand[pos >> 5] >> (pos & 31)) & 1u);
+              const bool in = pos < nIT && (mk || ((s_cand[pos >> 5] >> (pos & 31)) & 1u));
               bool ic = false, fi = false, of = false;
               if (in) {
-                if (fbit(s_firr, pos)) {
+                if (mk) {
+                  ic = fbit(tm_ic, pos);
+                  of = fbit(tm_of, pos);
+                } else if (fbit(s_firr, pos)) {
                   const int it = D.tpl_its[tb + pos];
                   ic = rs_intersects(L, D.it_rs + (int64_t)it * d.RSW, s_rs);
                   of = has_offering(it, s_rs);
@@ -2523,9 +2617,22 @@ struct Solver : ClaimSort {
               const uint64_t m = wballot(ic && fi && of);
               store_bits(s_rem, base, m);
               any |= m;
+              if constexpr (TPL_MASKS) {
+                if (mfill) {
+                  store_bits(tm_ic, base, wballot(ic));
+                  store_bits(tm_of, base, wballot(of));
+                }
+              }
+            }
+            if constexpr (TPL_MASKS) {
+              if (mfill) {
+                s_tmv[t] = 1u;  // wave-wide store of a uniform value
+                maskFills++;
+              }
             }
             algbytes += 4 * d.RSW + (int64_t)nIT * (8 * R() + 4 * d.RSW + 16);
             wsync();
+            YPH_END(tyl, YS_TPL_FILTER);
             if (any == 0) {
               code = FC_NO_IT | (flags << 8);
               if (!SIM && TOPO && t_any) {  // the message prints the requirements the topology narrowed
@@ -2573,6 +2680,7 @@ struct Solver : ClaimSort {
                 }
               }
               XPH_END(ttd1, SS_TPL_DERIVE);
+              YPH_END(ttd1, YS_TPL_THR);
               PH_BEGIN(tts1);
               // wave-wide stores of uniform values (see commit_claim)
               for (int r = 0; r < R(); r++) {
@@ -2615,6 +2723,7 @@ struct Solver : ClaimSort {
                 wsync();
                 memoHits++;
               } else {
+                if (mk) maskHits++;
                 if (inl) recompute_max<true>(c, s_rem, t, c);
                 else recompute_max<false>(c, s_rem, t, c);
                 if constexpr (TPL_MEMO) {
@@ -3355,6 +3464,11 @@ static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO,
   pl.talloc = (wideKO < 2 && tablesB + 64 * (posB + clmB) <= avail) ? 1 : 0;
   pl.tsort = pl.talloc && !d.negReq;
   if (pl.talloc) avail -= tablesB;
+  // The LEAN Solve's per-template requirement / offering bitsets (KS_TPL_MASKS), when they too leave room for 64
+  // claims; without them a NewNodeClaim that misses the memo derives both again.
+  const size_t tmaskB = tpl_mask_bytes(d.NTPL, (int)TW);
+  pl.tmask = (KS_TPL_MASKS && !sim && d.lean && pl.talloc && tpl_mask_fits(avail, d.NTPL, (int)TW, posB, clmB)) ? 1 : 0;
+  if (pl.tmask) avail -= tmaskB;
   const size_t kAll = avail / (posB + clmB);
   size_t ko, kl;
   if (kAll >= (size_t)d.Kcap) {
@@ -3369,11 +3483,13 @@ static Plan make_plan_live(const KsDims& d, size_t budget, bool sim, int wideKO,
   pl.KO = (int)ko;
   pl.KL = (int)kl;
   pl.lds = fixed + tclB + tdlB + livB + 3 * r16(4 * ko) + r16(8 * ko * R) + 2 * r16(4 * kl) + 2 * r16(8 * kl * R) + r16(4 * kl * TW) +
-           r16(4 * kl * R) + (pl.tsort ? tsortB : 0) + (pl.talloc ? tallocB : 0);
+           r16(4 * kl * R) + (pl.tsort ? tsortB : 0) + (pl.talloc ? tallocB : 0) + (pl.tmask ? tmaskB : 0);
   return pl;
 }
 
 int run_fuse_build() { return KS_RUN_FUSE; }
+int tpl_masks_build() { return KS_TPL_MASKS; }
+int log_runs_build() { return KS_LOG_RUNS && KS_CLAIM_RUNS; }
 int sort_leaf_build() { return KS_SORT_LEAF && !KS_SORT_LANE0; }
 int closed_shift_build() { return KS_CLOSED_SHIFT && KS_SORT_CLOSED; }
 
@@ -3486,7 +3602,7 @@ hipError_t sim_run_lengths(const int32_t* podmap, const int32_t* entry_sim, cons
 hipError_t launch_solve(const KsDev& D, const KsWork* works_dev, int nrep, const Plan& pl, int32_t* qorder,
                         uint64_t* skeys, int32_t* svals, void* stemp, size_t stempBytes, hipStream_t st,
                         hipEvent_t mid, const int32_t* fixed_order, hipEvent_t* feas, int32_t* run_len,
-                        uint64_t* run_words) {
+                        uint64_t* run_words, hipEvent_t post) {
   if (pl.lds > 160 * 1024) return hipErrorInvalidValue;
   if (!fixed_order) {
     hipError_t e = queue_sort(D, skeys, svals, stemp, stempBytes, qorder, st);
@@ -3510,7 +3626,18 @@ hipError_t launch_solve(const KsDev& D, const KsWork* works_dev, int nrep, const
   hipLaunchKernelGGL(k_init, dim3(512), dim3(256), 0, st, D, works_dev, nrep,
                      fixed_order ? fixed_order : (const int32_t*)qorder);
   if (mid) (void)hipEventRecord(mid, st);
-  return (D.d.G ? launch_solve_topo : launch_solve_plain)(D, works_dev, nrep, pl, st);
+  hipError_t e = (D.d.G ? launch_solve_topo : launch_solve_plain)(D, works_dev, nrep, pl, st);
+  if (post) (void)hipEventRecord(post, st);  // k_solve ends here
+  // KS_LOG_RUNS: a LEAN Solve (launch_family's choice) logged its long runs as records; their entries are written now.
+  // The grid is fixed by P -- the record count stays on the device.
+  const bool leanRoute = !D.d.G && D.d.lean && pl.talloc && (D.d.R == 3 || D.d.R == 4);
+  if (e == hipSuccess && log_runs_build() && leanRoute && nrep > 0 && D.d.P > 0) {
+    const int bx = std::min(256, std::max(1, (D.d.P + 255) / 256)), by = std::min(nrep, 1024);
+    hipLaunchKernelGGL(k_log_expand, dim3(bx, by), dim3(256), 0, st, works_dev, nrep,
+                       fixed_order ? fixed_order : (const int32_t*)qorder, D.d.P);
+    e = hipGetLastError();
+  }
+  return e;
 }
 
 // A batch of consolidation simulations (one wavefront each); their pod_map lists must already be

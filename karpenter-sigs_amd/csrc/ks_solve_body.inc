@@ -52,6 +52,13 @@
   constexpr bool MEMO = Solver<RT, TL, SIM, TOPO, LEAN>::TPL_MEMO;
   S.s_memo = (LU32)take(MEMO ? 4 * (size_t)tpl_memo_words(R, d.TW) : 0);
   if constexpr (MEMO) S.s_memo[S.MM_T] = (uint32_t)-1;  // empty (wave-wide store of a uniform value)
+  constexpr bool MASKS = Solver<RT, TL, SIM, TOPO, LEAN>::TPL_MASKS;
+  S.s_tmask = (LU32)take(MASKS && pl.tmask ? 4 * (size_t)tpl_mask_words(d.NTPL, d.TW) : 0);
+  S.s_tmv = (LU32)take(MASKS && pl.tmask ? 4 * (size_t)d.NTPL : 0);
+  if constexpr (MASKS) {
+    if (pl.tmask)
+      for (int i = lane(); i < d.NTPL; i += kWave) S.s_tmv[i] = 0;  // no row filled yet
+  }
   constexpr bool FRONT = Solver<RT, TL, SIM, TOPO, LEAN>::RUN_FRONT;
   S.s_fbeg = (LI32)take(FRONT ? 4 * (size_t)(d.NTPL + 1) : 0);
   S.s_front = (LI32)take(FRONT ? 4 * (size_t)D.frontTotal : 0);
@@ -1157,6 +1164,11 @@
                     if (wi + k <= wn) {  // the run's pods are the window's next lanes
                       const int src = wi + lane() < kWave ? wi + lane() : kWave - 1;
                       S.log_batch(k, __shfl(w.p, src), c, nlog);
+                    } else if constexpr (Solver<RT, TL, SIM, TOPO, LEAN>::LOG_RUNS) {
+                      // past the window: nothing was pushed back yet (only an ident run reaches here), so the run's
+                      // pods are NewQueue's order from qhead on and one record describes its entries
+                      S.log_run_record(k, qhead, c, nlog);
+                      SYPH_END(S, tlg, YS_LOG_STORE);
                     } else if constexpr (KS_LOG_AHEAD) {
                       // past the window: the queue holds them (nothing pushed back yet).  Up to four 64-pod chunks
                       // are loaded before the first is stored: a load waits for the stores issued before it as well
@@ -1181,8 +1193,13 @@
                       for (int b = 0; b < k; b += kWave) {
                         int pos = qhead + b + lane();
                         pos = pos >= P ? pos - P : pos;
+                        PH_BEGIN(tyq);
                         const int pv = b + lane() < k ? W.queue[pos] : 0;
+                        PH_WAIT_LOADS();
+                        SYPH_END(S, tyq, YS_LOG_LOAD);
+                        PH_BEGIN(tyb);
                         S.log_batch(k - b < kWave ? k - b : kWave, pv, c, nlog);
+                        SYPH_END(S, tyb, YS_LOG_STORE);
                       }
                     }
                     SXPH_END(S, tlg, SS_LOG);
@@ -1301,6 +1318,9 @@
     W.counters[CT_RUN_CAP_FULL] = S.capFull;
     W.counters[CT_RUN_CROSS_CLOSED] = crossClosed;
     W.counters[CT_RUN_MOVES] = runMoves;
+    W.counters[CT_TPL_MASK_FILLS] = S.maskFills;
+    W.counters[CT_TPL_MASK_HITS] = S.maskHits;
+    W.counters[CT_RUN_RECS] = S.runRecs;
 #ifdef KS_PHASE_STATS
     for (int i = 0; i < 7; i++) W.counters[CT_CYC_POP + i] = (int64_t)cyc[i];
     W.counters[CT_CYC_TOTAL] = (int64_t)(__builtin_amdgcn_s_memtime() - tstart);
@@ -1310,6 +1330,7 @@
     for (int i = 0; i < 12; i++) W.counters[CT_STEP + i] = (int64_t)S.xcyc[i];
     for (int i = 0; i < 3; i++) W.counters[CT_CYC_EXACT_BY_N + i] = (int64_t)S.ecyc[i];
     W.counters[CT_CLOSED_SHIFT_DIFF] = S.shiftDiff;
+    for (int i = 0; i < 6; i++) W.counters[CT_CYC_SPLIT + i] = (int64_t)S.ycyc[i];
 #endif
   }
   if constexpr (SIM) S.sim_record(P, nclaims, hostCtr, allSched, err, !ident, anyRelaxed);

@@ -27,6 +27,9 @@ for k in ["cycPop", "cycNodes", "cycNodeCommit", "cycSort", "cycQuick", "cycFull
           # the step's sub-phases: inside cycSort, cycCommit and cycTemplates
           "cycSortFast", "cycSortExact", "cycSortClosed", "cycRunCap", "cycCross", "cycBulk", "cycLog",
           "cycTplDerive", "cycTplStore", "cycTplMax",
+          # cycTplDerive and cycLog split further: candidates + tpl_rs copy, feas_masks, the filter loop, thresholds +
+          # front test; a run's queue loads past the window, its log entries (or its record)
+          "cycTplCand", "cycTplFeas", "cycTplFilter", "cycTplThr", "cycLogLoad", "cycLogStore",
           # the exact re-sorts by size (inside cycSortExact)
           "cycSortExactLe12", "cycSortExactLt50", "cycSortExactGe50"]:
     if k in st:
@@ -35,6 +38,7 @@ closed, exact = st["sortsClosed"], st["sortsExact"]
 print("re-sorts with a descent %d: fast %d exact %d closed %d;  n <= 12: %d, 12 < n < 50: %d, n >= 50: %d;  tplMemoHits %d" % (
     st["sortsWithDescent"], st["sortsWithDescent"] - exact - closed, exact, closed, st["sortsLe12"], st["sortsLt50"],
     st["sortsWithDescent"] - st["sortsLe12"] - st["sortsLt50"], st["tplMemoHits"]))
+print("tplMaskFills %s tplMaskHits %s runRecs %s" % (st.get("tplMaskFills"), st.get("tplMaskHits"), st.get("runRecs")))
 if closed:
     print("cycles per closed re-sort %.0f;  closedShiftDiff %s (moved entries whose shifted value differs from a regather)" % (
         st["cycSortClosed"] / closed, st.get("closedShiftDiff", "n/a")))
