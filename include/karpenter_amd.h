@@ -70,7 +70,8 @@ int ks_problem_check_binary(const void* buf, size_t len);
 
 /* Host-only encode of a snapshot (no device needed): returns JSON with the universe sizes (keys,
  * value words, resources "R", instance types, relaxation states), "lean" / "negReq" (resource-only pods /
- * some negative request), "plans" (the LDS plan at the default and a few reduced budgets), "FNR" (relaxation
+ * some negative request), "plans" (the LDS plan at the default and a few reduced budgets), "widePlans" (per budget of "plans", the two
+ * plans ks_solve re-plans to when a Solve outgrows the plan's NodeClaim capacity "KO"), "FNR" (relaxation
  * states with label requirements: the rows of k_feasibility_nodes), "keyValues" (per key of "keyNames", the
  * size of its value universe) and "coveredKeys" (the keys k_feasibility's rows decide).
  * Diagnostics / CPU tests. */
@@ -148,7 +149,9 @@ void ks_results_free(ks_results* r);
  * "tl": 0 | 1 (instance-type tables LDS-resident), "lean": 0 | 1 (the resource-only instantiation),
  * "n": work items, "launches": [the same fields for every launch of this Solve, in order]}.  A Solve that
  * re-plans (a lean Solve leaving for the non-lean code, a wider NodeClaim plan) has one entry per launch;
- * the outer fields are the last launch's.  Free with ks_free. */
+ * the outer fields are the last launch's.  "stats"."plan" is that launch's LDS plan: {"wide": 0 | 1 | 2 (the
+ * re-plan level for NodeClaim capacity), "KO" (NodeClaims per Solve), "KL" (of them LDS-resident), "talloc",
+ * "lds" (bytes)}.  Free with ks_free. */
 int ks_results_json(const ks_results* r, char** json_out);
 
 /* Structured accessors for a cgo shim (no JSON on the hot return path). */

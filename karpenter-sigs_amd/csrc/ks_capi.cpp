@@ -189,6 +189,8 @@ struct ks_results {
   };
   ks_problem* pb = nullptr;  // a reference on the problem the lazy rendering reads (ks_problem_free defers)
   std::vector<ks::Route> routes;  // the k_solve launches of this Solve, in order (a re-plan adds one)
+  ks::Plan plan{};                // the LDS plan of the last launch, and its make_plan level (wideKO)
+  int planWide = 0;
   // First-use rendering writes the claims' caches: serialised, so two threads reading one Results (ctypes
   // and cgo release the interpreter / scheduler around the call) render once; what a call hands out is
   // never rebuilt afterwards.
@@ -276,6 +278,13 @@ std::string queue_inputs_json(const Host& h) {
   return o;
 }
 }  // namespace ks
+
+// Whether a Solve computes the node rows (k_feasibility_nodes over FNR relaxation states): dims.fnOn, which
+// make_plan reads (one LDS word per 32 nodes), so ks_problem_inspect plans with the same value without an upload.
+static bool node_rows_on(const KsDims& d, size_t FNR) {
+  const size_t fnBytes = 4 * FNR * (((size_t)d.N + 31) / 32);
+  return FNR > 0 && d.N > 0 && fnBytes <= ((size_t)1 << 29) && !getenv("KS_NO_NODE_ROWS");
+}
 
 void ks_upload(ks_problem* pb) {
   Host& h = pb->host;
@@ -432,7 +441,7 @@ void ks_upload(ks_problem* pb) {
   const size_t NWN = ((size_t)h.dims.N + 31) / 32;
   const size_t fnBytes = 4 * (size_t)FNR * NWN;
   h.dims.FNR = FNR;
-  h.dims.fnOn = FNR > 0 && h.dims.N > 0 && fnBytes <= ((size_t)1 << 29) && !getenv("KS_NO_NODE_ROWS");
+  h.dims.fnOn = node_rows_on(h.dims, FNR);
   pb->fnBytes = 0;
   if (h.dims.fnOn) {
     for (int i = 0; i < FNR; i++) {
@@ -743,6 +752,11 @@ static void finish_json(const Host& h, const ks_results::Claim& cl) {
   cl.jsonDone = true;
 }
 
+// KE_CLAIM_CAP after the last launch of a Solve: lastKO is the largest capacity ks_solve's re-plans reached
+static KsError claim_cap_error(const ks_problem* pb) {
+  return KsError(KS_ERR_CAPACITY, "NodeClaim capacity (" + std::to_string(pb->lastKO) + " per Solve at this LDS budget) exceeded");
+}
+
 // Rebuild Results from the replica-0 workspace.
 static ks_results* collect(ks_problem* pb, const KsWork& W) {
   PhaseTimer pt("collect");
@@ -752,11 +766,8 @@ static ks_results* collect(ks_problem* pb, const KsWork& W) {
   std::vector<int64_t> ctr;
   dl(ctr, W.counters, CT_NCOUNTERS, st);
   HIPCHK(hipStreamSynchronize(st));
-  if (ctr[CT_ERROR] != KE_OK)
-    throw KsError(ctr[CT_ERROR] == KE_CLAIM_CAP ? KS_ERR_CAPACITY : KS_ERR_INTERNAL,
-                  ctr[CT_ERROR] == KE_CLAIM_CAP ? "NodeClaim capacity (" + std::to_string(pb->lastKO) +
-                                                      " per Solve at this LDS budget) exceeded"
-                                                : "solve kernel iteration cap hit");
+  if (ctr[CT_ERROR] == KE_CLAIM_CAP) throw claim_cap_error(pb);
+  if (ctr[CT_ERROR] != KE_OK) throw KsError(KS_ERR_INTERNAL, "solve kernel iteration cap hit");
   int nc = (int)ctr[CT_NCLAIMS], nl = (int)ctr[CT_NLOG];
   std::vector<int32_t> order, ctpl, chost, logp, logt, status, fstate;
   std::vector<int64_t> creq;
@@ -1204,13 +1215,23 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   o += "]";
   o += ",\"plans\":{";
   const size_t budgets[] = {160 * 1024 - 256, 6000, 9000, 14000, 24000, 40000};
-  for (size_t i = 0; i < sizeof(budgets) / sizeof(budgets[0]); i++) {
-    Plan pl = make_plan(d, budgets[i], false, 0, (int)frontPos.size());
-    o += (i ? ",\"" : "\"") + std::to_string(budgets[i]) + "\":{\"KO\":" + std::to_string(pl.KO) +
-         ",\"KL\":" + std::to_string(pl.KL) + ",\"talloc\":" + std::to_string(pl.talloc) +
-         ",\"tsort\":" + std::to_string(pl.tsort) + ",\"tmask\":" + std::to_string(pl.tmask) +
-         ",\"tmaskBytes\":" + std::to_string(pl.tmask ? tpl_mask_bytes(d.NTPL, d.TW) : 0) + ",\"lds\":" + std::to_string(pl.lds) + "}";
-  }
+  long long fnr = 0;
+  for (int32_t f : h.tab.st_flags) fnr += (f & SF_HAS_KEYS) ? 1 : 0;
+  KsDims pd = d;  // as ks_upload completes them
+  pd.fnOn = node_rows_on(d, (size_t)fnr);
+  auto plan_json = [&](size_t budget, int wide) {
+    Plan pl = make_plan(pd, budget, false, wide, (int)frontPos.size());
+    return "{\"KO\":" + std::to_string(pl.KO) +
+           ",\"KL\":" + std::to_string(pl.KL) + ",\"talloc\":" + std::to_string(pl.talloc) +
+           ",\"tsort\":" + std::to_string(pl.tsort) + ",\"tmask\":" + std::to_string(pl.tmask) +
+           ",\"tmaskBytes\":" + std::to_string(pl.tmask ? tpl_mask_bytes(d.NTPL, d.TW) : 0) + ",\"lds\":" + std::to_string(pl.lds) + "}";
+  };
+  for (size_t i = 0; i < sizeof(budgets) / sizeof(budgets[0]); i++)
+    o += (i ? ",\"" : "\"") + std::to_string(budgets[i]) + "\":" + plan_json(budgets[i], 0);
+  // the plans ks_solve re-plans to when a Solve outgrows KO (make_plan's wideKO levels 1 and 2), per budget
+  o += "},\"widePlans\":{";
+  for (size_t i = 0; i < sizeof(budgets) / sizeof(budgets[0]); i++)
+    o += (i ? ",\"" : "\"") + std::to_string(budgets[i]) + "\":[" + plan_json(budgets[i], 1) + "," + plan_json(budgets[i], 2) + "]";
   o += "}";
   o += ",\"keyNames\":[";
   for (size_t i = 0; i < h.keyNames.size(); i++) { if (i) o += ","; ksjson::quote(o, h.keyNames[i]); }
@@ -1218,8 +1239,6 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   for (size_t i = 0; i < h.resNames.size(); i++) { if (i) o += ","; ksjson::quote(o, h.resNames[i]); }
   // what the feasibility kernels' shapes depend on: the node rows (states with label requirements), the value
   // universe of every key, and the keys k_feasibility's rows decide (no instance type holds two values)
-  long long fnr = 0;
-  for (int32_t f : h.tab.st_flags) fnr += (f & SF_HAS_KEYS) ? 1 : 0;
   o += "],\"FNR\":" + std::to_string(fnr) + ",\"keyValues\":[";
   for (size_t i = 0; i < h.keys.size(); i++) o += (i ? "," : "") + std::to_string(h.keys[i].nv);
   o += "],\"coveredKeys\":[";
@@ -1483,6 +1502,7 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   // (kernel_ms: everything launch_solve launched, k_log_expand included; solve_ms: k_solve alone, em to ep)
   float ms = 0, setup = 0, post = 0, fms = 0, fnms = 0;
   int feasLaunches = 0, attempts = 0;
+  int wide = pb->wideKO;  // make_plan's level of pl
   std::vector<Route> routes;
   RouteScope routeScope(&routes);
   for (int attempt = 0; attempt < 4; attempt++) {
@@ -1518,15 +1538,20 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
       pb->dev.d.lean = 0;
       continue;
     }
-    if (err != KE_CLAIM_CAP || pb->wideKO >= 2) break;
+    if (err != KE_CLAIM_CAP) break;
     // more NodeClaims than the plan holds: re-plan with claim positions filling the LDS (level 1 keeps the
-    // instance-type tables in LDS, level 2 moves them to HBM; remembered for later Solves of this problem)
-    // and solve again
-    const int prevKO = pl.KO;
-    pb->wideKO++;
-    pl = make_plan(d, budget, false, pb->wideKO, pb->dev.frontTotal);
-    if (pb->wideKO == 1 && pl.KO <= prevKO) pl = make_plan(d, budget, false, pb->wideKO = 2, pb->dev.frontTotal);
-    if (pl.lds > 160 * 1024 || pl.KO < 1) break;
+    // instance-type tables in LDS, level 2 moves them to HBM) and solve again.  At a small budget a wide plan can
+    // hold fewer positions than the plan that just ran (make_plan): a level is launched, and remembered for later
+    // Solves of this problem, only when it raises KO; when none does, the Solve fails with the KO that ran.
+    int next = wide + 1;
+    Plan np{};
+    for (; next <= 2; next++) {
+      np = make_plan(d, budget, false, next, pb->dev.frontTotal);
+      if (np.lds <= 160 * 1024 && np.KO > pl.KO) break;
+    }
+    if (next > 2) break;
+    pl = np;
+    wide = pb->wideKO = next;
     pb->lastKO = pl.KO;
   }
   (void)hipEventDestroy(e0);
@@ -1540,15 +1565,18 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
     dl(r->counters, w0.counters, CT_NCOUNTERS, pb->stream);
     HIPCHK(hipStreamSynchronize(pb->stream));
     if (r->counters[CT_ERROR] != KE_OK) {
-      std::string msg = "solve kernel reported error " + std::to_string(r->counters[CT_ERROR]);
+      const int64_t err = r->counters[CT_ERROR];
       delete r;
-      throw KsError(KS_ERR_INTERNAL, msg);
+      if (err == KE_CLAIM_CAP) throw claim_cap_error(pb);  // (as collect reports it)
+      throw KsError(KS_ERR_INTERNAL, "solve kernel reported error " + std::to_string(err));
     }
     r->algbytes = (double)r->counters[CT_ALGBYTES];
   } else {
     r = collect(pb, w0);
   }
   r->routes = routes;
+  r->plan = pl;
+  r->planWide = wide;
   r->kernel_ms = ms;
   r->solve_ms = ms - setup - post;
   r->feas_ms = fms;
@@ -1605,6 +1633,10 @@ int ks_results_json(const ks_results* r, char** json_out) {
     std::string last = routes_json({r->routes.back()});
     o += ",\"route\":" + last.substr(1, last.size() - 3) + ",\"launches\":" + routes_json(r->routes) + "}";
   }
+  // the LDS plan of the last launch ("wide": make_plan's level, above 0 after a re-plan for NodeClaim capacity)
+  o += ",\"plan\":{\"wide\":" + std::to_string(r->planWide) + ",\"KO\":" + std::to_string(r->plan.KO) +
+       ",\"KL\":" + std::to_string(r->plan.KL) + ",\"talloc\":" + std::to_string(r->plan.talloc) +
+       ",\"lds\":" + std::to_string(r->plan.lds) + "}";
   o += "}}";
   *json_out = strdup(o.c_str());
   return KS_OK;
