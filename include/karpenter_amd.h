@@ -123,6 +123,15 @@ int ks_problem_queue_readback(ks_problem* p, int32_t** order, int32_t** run_len,
  * with Go's pdqsort_func (*how 1). */
 int ks_claim_sort_probe(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
                         const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead, int* how);
+/* The same with the path the general re-sort took in *path (may be NULL): 0 none (the closed form, or a build
+ * without the register copy), 1 it finished on the copy held in registers (up to 64 entries as shipped, 128 in a
+ * -DKS_SORT_REGS_N64=0 build), 2 the copy was abandoned on a failed invariant, 3 the array has more entries than the
+ * copy holds (2 and 3: the LDS code sorted it).  device -3: the host's lane model of the 64-entry copy in place of
+ * Go's pdqsort_func (-2: of the 128-entry form); *path then also holds its breakPatterns calls << 8 and its heapSort
+ * calls << 20. */
+int ks_claim_sort_probe_path(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
+                             const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead,
+                             int* how, int* path);
 /* k_rec_headers (the device-side record invariants and header compaction of a consolidation pass) without a
  * handle.  records: the passes' record batches back to back, pass i holding pass_ns[i] records of RF_HDR + 3 * TW
  * int32 words; tpl_beg: ntpl + 1 offsets, template t's instance-type list has tpl_beg[t + 1] - tpl_beg[t] <= 32 * TW

@@ -1205,7 +1205,8 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   pareto_fronts(d, h.tab.tpl_it_beg, h.tab.tpl_its, h.tab.it_alloc, frontBeg, frontPos);
   o += ",\"runFuse\":" + std::to_string(run_fuse_build()) + ",\"sortLeaf\":" + std::to_string(sort_leaf_build()) +
        ",\"closedShift\":" + std::to_string(closed_shift_build()) + ",\"tplMasks\":" + std::to_string(tpl_masks_build()) +
-       ",\"logRuns\":" + std::to_string(log_runs_build()) + ",\"paretoFronts\":[";
+       ",\"logRuns\":" + std::to_string(log_runs_build()) + ",\"sortRegs\":" + std::to_string(sort_regs_build()) +
+       ",\"sortRegsN64\":" + std::to_string(sort_regs_n64_build()) + ",\"queuePacked\":" + std::to_string(queue_packed_build()) + ",\"paretoFronts\":[";
   for (int t = 0; t < d.NTPL; t++) {
     o += t ? ",[" : "[";
     for (int i = frontBeg[(size_t)t]; i < frontBeg[(size_t)t + 1]; i++)
@@ -1402,9 +1403,22 @@ int ks_problem_queue_readback(ks_problem* pb, int32_t** order, int32_t** run_len
 // with device < 0 its expected value from Go's pdqsort_func on the host (ks_sort_probe.h).  No problem, no Solve.
 int ks_claim_sort_probe(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
                         const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead, int* how) {
+  return ks_claim_sort_probe_path(device, mode, pos, n, R, keys, order, claim_tpl, claim_head, ptpl, phead, how, nullptr);
+}
+// ... with the general re-sort's path (register copy or LDS code); device -2 / -3: the register copy's lane model
+// on the host (ks_sort_regs.h), 128 / 64 entries
+int ks_claim_sort_probe_path(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
+                             const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead,
+                             int* how, int* path) {
   API_TRY
   if (const char* bad = sort_probe_check(mode, pos, n, R, keys, order, claim_tpl, claim_head, ptpl, phead))
     throw KsError(KS_ERR_ARG, bad);
+  if (path) *path = 0;
+  if (device == -2 || device == -3) {
+    const int h = sort_probe_model(n, R, keys, order, claim_tpl, claim_head, ptpl, phead, device == -2, path);
+    if (how) *how = h;
+    return KS_OK;
+  }
   if (device < 0) {
     sort_probe_host(n, R, keys, order, claim_tpl, claim_head, ptpl, phead);
     if (how) *how = 1;
@@ -1440,16 +1454,17 @@ int ks_claim_sort_probe(int device, int mode, int pos, int n, int R, int32_t* ke
     HIPCHK(hipMemcpyAsync(b.chead, claim_head, 8 * (size_t)n * R, hipMemcpyHostToDevice, b.stream));
   }
   HIPCHK(claim_sort_probe(b.keys, b.order, n, mode, pos, R, b.ctpl, b.chead, b.ptpl, b.phead, b.how, b.stream));
-  int32_t h = -1;
+  int32_t h[2] = {-1, 0};  // how, path
   if (n > 0) {
     HIPCHK(hipMemcpyAsync(keys, b.keys, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipMemcpyAsync(order, b.order, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipMemcpyAsync(ptpl, b.ptpl, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipMemcpyAsync(phead, b.phead, 8 * (size_t)n * R, hipMemcpyDeviceToHost, b.stream));
   }
-  HIPCHK(hipMemcpyAsync(&h, b.how, 4, hipMemcpyDeviceToHost, b.stream));
+  HIPCHK(hipMemcpyAsync(h, b.how, 8, hipMemcpyDeviceToHost, b.stream));
   HIPCHK(hipStreamSynchronize(b.stream));
-  if (how) *how = h;
+  if (how) *how = h[0];
+  if (path) *path = h[1];
   return KS_OK;
   API_CATCH
 }
@@ -1624,7 +1639,7 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "cycRunCap", "cycCross", "cycBulk", "cycLog", "cycTplDerive", "cycTplStore",
                                 "cycTplMax", "runCapFront", "runCapFull", "runCrossClosed", "runMoves",
                                 "cycSortExactLe12", "cycSortExactLt50", "cycSortExactGe50", "closedShiftDiff",
-                                "tplMaskFills", "tplMaskHits", "runRecs",
+                                "tplMaskFills", "tplMaskHits", "runRecs", "sortsRegs", "sortRegsBail", "sortRegsOver",
                                 "cycTplCand", "cycTplFeas", "cycTplFilter", "cycTplThr", "cycLogLoad", "cycLogStore"};
   static_assert(sizeof(names) / sizeof(names[0]) == CT_NCOUNTERS, "one name per counter");
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);

@@ -355,6 +355,10 @@ enum Counter {
   CT_TPL_MASK_FILLS,  // LEAN Solve: templates whose requirement / offering bitsets were derived and kept (KS_TPL_MASKS)
   CT_TPL_MASK_HITS,   // ... and NewNodeClaims that missed the memo and read them
   CT_RUN_RECS,        // LEAN Solve: runs logged as one record for k_log_expand (KS_LOG_RUNS)
+  CT_SORT_REGS,       // LEAN Solve: general claim re-sorts finished on the register copy (KS_SORT_REGS: up to 64 claims
+                      // as shipped, 128 with -DKS_SORT_REGS_N64=0)
+  CT_SORT_REGS_BAIL,  // ... those the copy abandoned on a failed invariant (0: anything else is a bug) ...
+  CT_SORT_REGS_OVER,  // ... and those with more claims than the copy holds; both kinds are sorted by the LDS code
   // diagnostic build: SS_TPL_DERIVE and SS_LOG split further (cycles): the candidate loop with the tpl_rs copy,
   // feas_masks, the filter loop (Fits and the flags), the thresholds with the front test; a run's queue loads past
   // the window (waited for), its log_batch calls or its record

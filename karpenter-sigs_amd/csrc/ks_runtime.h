@@ -32,7 +32,10 @@ int sort_leaf_build();     // ... and KS_SORT_LEAF ("sortLeaf"), KS_CLOSED_SHIFT
 int closed_shift_build();
 int tpl_masks_build();     // KS_TPL_MASKS ("tplMasks"), KS_LOG_RUNS ("logRuns")
 int log_runs_build();
-// ks_claim_sort_probe's kernel (ks_solve.hip): device pointers, how [64]; n <= kProbeMaxN, R 3 or 4
+int sort_regs_build();     // KS_SORT_REGS ("sortRegs") and its n <= 64 form, KS_SORT_REGS_N64 ("sortRegsN64")
+int sort_regs_n64_build();
+int queue_packed_build();  // KS_QUEUE_PACKED ("queuePacked", ks_queue.hip)
+// ks_claim_sort_probe's kernel (ks_solve.hip): device pointers, how [64] (how, path); n <= kProbeMaxN, R 3 or 4
 hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,
                             const int64_t* chead, int32_t* ptpl, int64_t* phead, int32_t* how, hipStream_t st);
 // frontTotal: KsDev::frontTotal, the Pareto-front positions a LEAN Solve keeps in LDS

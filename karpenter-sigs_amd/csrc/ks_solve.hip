@@ -74,6 +74,17 @@
 #ifndef KS_SORT_OUTLINE  // the general claim re-sort as one out-of-line function per kernel (0: inlined at both call sites)
 #define KS_SORT_OUTLINE 1
 #endif
+// LEAN Solve: the general claim re-sort of up to 128 claims runs on a copy held in registers (ks_sort_regs.h) and
+// stores it once; anything else, or a failed invariant, leaves the arrays to the LDS code (0: the LDS code alone).
+// KS_SORT_REGS_N64: 1 restricts it to n <= 64, one register pair per lane (0: 128, two pairs).  Measured on C2
+// against 6.519 ms: 6.218 ms with the 64-entry form, 6.411 ms with the 128-entry one, whose every step pays for the
+// second pair: the 64-entry form ships, 65 claims and more stay with the LDS code
+#ifndef KS_SORT_REGS
+#define KS_SORT_REGS 1
+#endif
+#ifndef KS_SORT_REGS_N64
+#define KS_SORT_REGS_N64 1
+#endif
 #ifndef KS_TPL_MEMO  // LEAN Solve: a NewNodeClaim reuses what the last one derived from the same template, state, requests
 #define KS_TPL_MEMO 1
 #endif
@@ -98,6 +109,7 @@
 #include "ks_gosort.h"
 #include "ks_problem.h"
 #include "ks_reqset.h"
+#include "ks_sort_regs.h"
 #include "ks_tplmask.h"
 
 namespace ks {
@@ -666,6 +678,8 @@ struct ClaimSort {
     }
     return n;
   }
+  // (the medians below are also choose_pivot_medians of ks_sort_regs.h, the register copy's: a change here is a
+  // change there; sharing one form changed the code of every k_solve instantiation)
   // choosePivot_func (zsortfunc.go): the wave reads the (up to) nine samples at once, lane t sample t,
   // and the medians run on scalars; same pivot and hint as GoSortT::choosePivot.
   __device__ __forceinline__ int w_choose_pivot(int a, int b, int& hint) const {
@@ -1078,13 +1092,48 @@ struct ClaimSort {
     }
   }
 };
+// The wave's operations for SortRegsT (ks_sort_regs.h)
+struct SortRegsWaveOps {
+  using Vec = int;
+  template <class F> static __device__ __forceinline__ void each(F f) { f(lane()); }
+  static __device__ __forceinline__ int& at(Vec& v, int) { return v; }
+  static __device__ __forceinline__ int get(const Vec& v, int) { return v; }
+  static __device__ __forceinline__ int rdl(Vec v, int l) { return __builtin_amdgcn_readlane(v, l); }
+  template <class F> static __device__ __forceinline__ uint64_t ballot(F p) { return wballot(p(lane())); }
+  template <class F> static __device__ __forceinline__ Vec gather(Vec v, F src) {
+    return __builtin_amdgcn_ds_bpermute(src(lane()) * 4, v);
+  }
+  template <class F> static __device__ __forceinline__ Vec scatter(Vec v, F dst) {
+    return __builtin_amdgcn_ds_permute(dst(lane()) * 4, v);
+  }
+};
 // The general re-sort: partialInsertionSort when choosePivot gave the increasing hint (pivot >= 0), else or after
 // it the exact pdqsort.  claim_sort_general_out is the same out of line (KS_SORT_OUTLINE), so a kernel holds one copy
 // for its two call sites; the arguments are the two LDS arrays, not the Solver (a pointer to which would force its
 // state into memory).
 // Returns tlo | (thi + 1) << 15 | done << 30 (positions < 2^14: KsDims::Kcap).
-template <bool LEAF>
+// REGS (KS_SORT_REGS; the LEAN Solve's out-of-line copy and the probe): up to kSortRegsMax entries are sorted on a
+// register copy, stored once, and the word carries kSortRegsDone; after a bail-out the arrays are as they were and
+// the LDS code below sorts them.
+template <bool LEAF, bool REGS = false>
 static __device__ __forceinline__ uint32_t claim_sort_general(LI32 okey, LI32 order, int n, int pivot) {
+  if constexpr (REGS && KS_SORT_REGS != 0) {
+    n = uni(n);
+    pivot = uni(pivot);
+    if (n <= (KS_SORT_REGS_N64 ? 64 : kSortRegsMax)) {
+      SortRegsT<SortRegsWaveOps, !KS_SORT_REGS_N64> rs;
+      rs.load(n, [&](int p) { return okey[p]; }, [&](int p) { return order[p]; });
+      const uint32_t g = rs.general(pivot);
+      if (g != 0) {
+        rs.store([&](int p, int k, int v) {
+          okey[p] = k;
+          order[p] = v;
+        });
+        wsync();
+        return g;
+      }
+    }
+  }
   ClaimSort cs;
   cs.s_order = order;
   cs.s_okey = okey;
@@ -1106,7 +1155,7 @@ static __device__ __forceinline__ uint32_t claim_sort_general(LI32 okey, LI32 or
   return (uint32_t)tlo | (uint32_t)(thi + 1) << 15 | (uint32_t)done << 30;
 }
 static __device__ __noinline__ uint32_t claim_sort_general_out(LI32 okey, LI32 order, int n, int pivot) {
-  return claim_sort_general<true>(okey, order, n, pivot);
+  return claim_sort_general<true, true>(okey, order, n, pivot);
 }
 
 template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN>
@@ -2805,6 +2854,10 @@ struct Solver : ClaimSort {
   static constexpr bool SORT_CLOSED = !SIM && (KS_SORT_CLOSED == 2 || (KS_SORT_CLOSED == 1 && LEAN));
   // (the LEAN Solve alone: its resource count is a compile-time 3 or 4, which the shift keeps in registers)
   static constexpr bool CLOSED_SHIFT = KS_CLOSED_SHIFT && SORT_CLOSED && LEAN && RT > 0;
+  // the general re-sort's register copy (KS_SORT_REGS: the LEAN Solve's out-of-line claim_sort_general_out)
+  static constexpr bool SORT_REGS = KS_SORT_REGS != 0 && KS_SORT_OUTLINE && LEAN && !SIM;
+  int sortsRegs = 0, sortRegsOver = 0, sortRegsBail = 0;  // general re-sorts finished from registers / too large for
+                                                          // the copy / abandoned on a failed invariant (0)
   int64_t shiftDiff = 0;  // diagnostic build: moved entries whose shifted s_ptpl / s_phead differ from a regather
   __device__ __forceinline__ int sort_claims(int n, int pos, int& npos) {
     int tlo = n, thi = -1, pivot = -1;
@@ -2847,6 +2900,12 @@ struct Solver : ClaimSort {
       tlo = (int)(g & 0x7fff);
       thi = (int)(g >> 15 & 0x7fff) - 1;
       done = g >> 30 & 1;
+      if constexpr (SORT_REGS) {  // more claims than the copy holds is expected; any other refusal is a bug signal
+        const bool over = n > (KS_SORT_REGS_N64 ? 64 : kSortRegsMax);
+        sortsRegs += (int)(g >> 31);
+        sortRegsOver += over ? 1 : 0;
+        sortRegsBail += !over && !(g >> 31) ? 1 : 0;
+      }
     }
     wsync();
 #ifdef KS_PHASE_STATS
@@ -3492,6 +3551,8 @@ int tpl_masks_build() { return KS_TPL_MASKS; }
 int log_runs_build() { return KS_LOG_RUNS && KS_CLAIM_RUNS; }
 int sort_leaf_build() { return KS_SORT_LEAF && !KS_SORT_LANE0; }
 int closed_shift_build() { return KS_CLOSED_SHIFT && KS_SORT_CLOSED; }
+int sort_regs_build() { return KS_SORT_REGS != 0 && KS_SORT_OUTLINE; }
+int sort_regs_n64_build() { return sort_regs_build() && KS_SORT_REGS_N64; }
 
 // Test / diagnostic kernel (ks_claim_sort_probe): Solver::sort_claims' logic on arrays of the caller's choosing,
 // one wave, no Solve.  keys / order [n] are loaded into LDS with the position arrays ptpl / phead gathered from the
@@ -3544,12 +3605,15 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_claim_sor
       }
     }
   }
+  int path = 0;  // the general re-sort's (KS_SORT_REGS): 1 finished on the register copy, 2 abandoned on a failed
+                 // invariant, 3 more entries than the copy holds (2 and 3: the LDS code sorted)
   if (closed) res = 2;
   else {
-    const uint32_t g = claim_sort_general<true>(cs.s_okey, cs.s_order, n, pivot);
+    const uint32_t g = claim_sort_general<true, true>(cs.s_okey, cs.s_order, n, pivot);
     tlo = (int)(g & 0x7fff);
     thi = (int)(g >> 15 & 0x7fff) - 1;
     res = g >> 30 & 1 ? 0 : 1;
+    path = g & kSortRegsDone ? 1 : KS_SORT_REGS == 0 ? 0 : n > (KS_SORT_REGS_N64 ? 64 : kSortRegsMax) ? 3 : 2;
   }
   wsync();
   gather(tlo, thi);
@@ -3559,7 +3623,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_claim_sor
     ptpl[j] = s_ptpl[j];
     for (int r = 0; r < R; r++) phead[(int64_t)j * R + r] = s_phead[(int64_t)j * R + r];
   }
-  how[lane()] = res;  // [kWave], one value
+  how[lane()] = lane() == 1 ? path : res;  // [kWave]: how, and in word 1 the path
 }
 // n <= kProbeMaxN positions, R 3 or 4 (the LEAN Solve's resource counts); the arrays are device pointers
 hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,

@@ -1321,6 +1321,11 @@
     W.counters[CT_TPL_MASK_FILLS] = S.maskFills;
     W.counters[CT_TPL_MASK_HITS] = S.maskHits;
     W.counters[CT_RUN_RECS] = S.runRecs;
+    if constexpr (decltype(S)::SORT_REGS) {  // (k_init zeroed them: the other instantiations' code stays as it was)
+      W.counters[CT_SORT_REGS] = S.sortsRegs;
+      W.counters[CT_SORT_REGS_BAIL] = S.sortRegsBail;
+      W.counters[CT_SORT_REGS_OVER] = S.sortRegsOver;
+    }
 #ifdef KS_PHASE_STATS
     for (int i = 0; i < 7; i++) W.counters[CT_CYC_POP + i] = (int64_t)cyc[i];
     W.counters[CT_CYC_TOTAL] = (int64_t)(__builtin_amdgcn_s_memtime() - tstart);

@@ -8,6 +8,7 @@
 
 #include "ks_gosort.h"
 #include "ks_problem.h"  // kProbeMaxN
+#include "ks_sort_regs.h"
 
 namespace ks {
 
@@ -35,6 +36,18 @@ inline void sort_probe_host(int n, int R, int32_t* keys, int32_t* order, const i
     ptpl[j] = claim_tpl[c];
     for (int r = 0; r < R; r++) phead[(size_t)j * R + r] = claim_head[(size_t)c * R + r];
   }
+}
+
+// The same from the lane model of the register-copy re-sort (ks_sort_regs.h: sort_regs_model, its how and *path)
+inline int sort_probe_model(int n, int R, int32_t* keys, int32_t* order, const int32_t* claim_tpl,
+                            const int64_t* claim_head, int32_t* ptpl, int64_t* phead, bool two, int* path) {
+  const int how = sort_regs_model(n, keys, order, two, path);
+  for (int j = 0; j < n; j++) {
+    const int c = order[j];
+    ptpl[j] = claim_tpl[c];
+    for (int r = 0; r < R; r++) phead[(size_t)j * R + r] = claim_head[(size_t)c * R + r];
+  }
+  return how;
 }
 
 }  // namespace ks

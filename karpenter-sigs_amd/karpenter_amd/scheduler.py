@@ -186,10 +186,13 @@ def rec_headers_run(passes, tw, tpl_beg):
     return out
 
 
-def claim_sort_probe(keys, order, claim_tpl, claim_head, mode=0, pos=-1, device=0):
+def claim_sort_probe(keys, order, claim_tpl, claim_head, mode=0, pos=-1, device=0, path=False):
     """Test / diagnostic (ks_claim_sort_probe): the Solve kernel's claim re-sort on arrays of the caller's choosing,
     or with device=-1 Go's pdqsort_func on the host.  claim_head is [n][R], R 3 or 4.  Returns (keys, order, ptpl,
-    phead, how) as numpy arrays and an int."""
+    phead, how) as numpy arrays and an int.  path=True (ks_claim_sort_probe_path) appends the general re-sort's path:
+    1 finished on the register copy, 3 more entries than the copy holds, 2 abandoned on a failed invariant (2 and 3:
+    sorted by the LDS code), 0 neither; device=-3 runs the lane model of the 64-entry copy on the host (-2: of the
+    128-entry form), the path then carrying its breakPatterns calls << 8 and heapSort calls << 20."""
     import numpy as np
 
     k = np.array(keys, dtype=np.int32)
@@ -202,6 +205,14 @@ def claim_sort_probe(keys, order, claim_tpl, claim_head, mode=0, pos=-1, device=
     pt = np.zeros(n, dtype=np.int32)
     ph = np.zeros((n, r), dtype=np.int64)
     how = ctypes.c_int(-1)
+    if path or device < -1:
+        pth = ctypes.c_int(0)
+        lib().ks_claim_sort_probe_path.argtypes = ([ctypes.c_int] * 5 + [ctypes.c_void_p] * 6 +
+                                                   [ctypes.POINTER(ctypes.c_int)] * 2)
+        _check(lib().ks_claim_sort_probe_path(device, mode, pos, n, r, k.ctypes.data, o.ctypes.data, ct.ctypes.data,
+                                              ch.ctypes.data, pt.ctypes.data, ph.ctypes.data, ctypes.byref(how),
+                                              ctypes.byref(pth)))
+        return (k, o, pt, ph, how.value, pth.value) if path else (k, o, pt, ph, how.value)
     # (bound here, not in lib(): an earlier commit's library, loaded for an A/B run, lacks the entry)
     lib().ks_claim_sort_probe.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 6 + [ctypes.POINTER(ctypes.c_int)]
     _check(lib().ks_claim_sort_probe(device, mode, pos, n, r, k.ctypes.data, o.ctypes.data, ct.ctypes.data,

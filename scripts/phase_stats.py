@@ -39,6 +39,8 @@ print("re-sorts with a descent %d: fast %d exact %d closed %d;  n <= 12: %d, 12 
     st["sortsWithDescent"], st["sortsWithDescent"] - exact - closed, exact, closed, st["sortsLe12"], st["sortsLt50"],
     st["sortsWithDescent"] - st["sortsLe12"] - st["sortsLt50"], st["tplMemoHits"]))
 print("tplMaskFills %s tplMaskHits %s runRecs %s" % (st.get("tplMaskFills"), st.get("tplMaskHits"), st.get("runRecs")))
+print("sortsRegs %s sortRegsOver %s sortRegsBail %s (general re-sorts finished on the register copy / with more claims "
+      "than it holds / abandoned on a failed invariant)" % (st.get("sortsRegs"), st.get("sortRegsOver"), st.get("sortRegsBail")))
 if closed:
     print("cycles per closed re-sort %.0f;  closedShiftDiff %s (moved entries whose shifted value differs from a regather)" % (
         st["cycSortClosed"] / closed, st.get("closedShiftDiff", "n/a")))
