@@ -95,6 +95,54 @@ int ks_problem_inspect(const char* snapshot_json, size_t len, char** dims_json);
  *     [the label keys the instance-type rows decide: those no instance type holds with more than one value]}. */
 int ks_problem_feasibility_rows(ks_problem* p, int which, char** meta_json, uint32_t** words, size_t* n_words);
 
+/* The static feasibility matrix: every relaxation state of every pod against every NodeClaimTemplate's instance
+ * types and every existing node, from the problem's static tables alone (no Solve).
+ *
+ * Template row (s, t): what Scheduler.add's template phase gives a fresh NodeClaim of template t for the pod of
+ * state s before any commit, tested in this order: the NodePool's remaining limits (FC_LIMITS), the template's
+ * taints (FC_TAINTS), Compatible + Add of the requirements (FC_COMPAT), then per instance type Intersects, Fits
+ * with the template's daemon overhead and an available offering (FC_NO_IT | filterResults flags << 8).  code is
+ * 0 when the row has options; count is their number; the TW words are the options as template positions (all
+ * zero in a failing row and past the template's list).
+ * Node row s: bit n is set iff existing node n accepts the pod on its initial state: taints tolerated, no host
+ * port conflict, Fits(node requests + pod, available), strict Compatible of the labels.  ceil(N / 32) words,
+ * bits past N zero; count is the number of set bits.
+ *
+ * Topology and volume limits are not evaluated ("ignores" in the meta document; it lists the states that own
+ * topology groups and carries "volAny"): for those the rows are an upper bound.  Within a Solve requests and
+ * host ports only grow, requirements only narrow and remaining limits only shrink, so a clear bit holds for
+ * every Solve of the problem; a set bit is exact for an empty scheduler without topology.  A problem with a
+ * negative request is refused with KS_ERR_UNSUPPORTED (Fits is not monotone then).
+ *
+ * where = 0: two kernels on the device the problem lives on (opts->device as for ks_solve; opts may be NULL),
+ * on the problem's stream; where = 1: the same definitions in plain loops on the host, no device call.
+ * ks_problem_create_host builds a problem without a device for where = 1 (ks_solve on it fails with KS_ERR_HIP).
+ *
+ * ks_feasibility_meta (free with ks_free): {"S", "NTPL", "N", "TW", "NWN", "podState0", "podNState", "statePod",
+ * "templates": [{"nodePool", "instanceTypes": [names in position order]}], "nodes": [names in device order],
+ * "ignores": ["topology", "volumeLimits"], "topologyStates": [states that own a topology group], "volAny",
+ * "codes": {"FC_NONE", "FC_LIMITS", "FC_TAINTS", "FC_COMPAT", "FC_NO_IT", "FF_REQ", "FF_FITS", "FF_OFF",
+ * "FF_REQ_FITS", "FF_REQ_OFF", "FF_FITS_OFF"}}.
+ * The row accessors return pointers into the handle (valid until ks_feasibility_free); KS_ERR_ARG for a state or
+ * template out of range.  ks_feasibility_timing: where = 0: the two kernels' time by events, the table bytes
+ * they address and the bytes of the rows they write; where = 1: kernel_ms 0 and the same byte counts. */
+typedef struct ks_feasibility ks_feasibility;
+int ks_problem_create_host(const char* snapshot_json, size_t len, ks_problem** out);
+int ks_problem_static_feasibility(ks_problem* p, const ks_solve_opts* opts, int where, ks_feasibility** out);
+void ks_feasibility_free(ks_feasibility* f);
+int ks_feasibility_meta(const ks_feasibility* f, char** meta_json);
+int ks_feasibility_template_row(const ks_feasibility* f, int state, int tpl, uint32_t* code, int32_t* count,
+                                const uint32_t** words, int* n_words);
+int ks_feasibility_node_row(const ks_feasibility* f, int state, int32_t* count, const uint32_t** words, int* n_words);
+int ks_feasibility_timing(const ks_feasibility* f, double* kernel_ms, int64_t* bytes_read, int64_t* bytes_written);
+/* Bulk view of the five arrays (what the Python mirror copies): tpl_code [S][NTPL], tpl_count [S][NTPL],
+ * tpl_options [S][NTPL][TW], node_bits [S][NWN], node_count [S]; dims: S, NTPL, N, TW, NWN.  Any pointer may be
+ * NULL. */
+int ks_feasibility_arrays(const ks_feasibility* f, int dims[5], const uint32_t** tpl_code, const int32_t** tpl_count,
+                          const uint32_t** tpl_options, const uint32_t** node_bits, const int32_t** node_count);
+/* The two kernels' times separately (where = 0; zeros for where = 1). */
+int ks_feasibility_kernel_times(const ks_feasibility* f, double* templates_ms, double* nodes_ms);
+
 /* Test and diagnostic entries: what the queue-preparation kernels (ks_queue.hip) read and write.  None of them
  * runs k_solve.
  *

@@ -12,6 +12,8 @@
 
 #include "../../include/karpenter_amd.h"
 #include "ks_archive.h"
+#include "ks_feas.h"
+#include "ks_feas_host.h"
 #include "ks_host.h"
 #include "ks_runtime.h"
 #include "ks_sort_probe.h"
@@ -1711,5 +1713,261 @@ double ks_results_feasibility_bytes(const ks_results* r) { return r->feas_bytes;
 double ks_results_node_feasibility_ms(const ks_results* r) { return r->feasn_ms; }
 double ks_results_node_feasibility_bytes(const ks_results* r) { return r->feasn_bytes; }
 double ks_results_algorithmic_bytes(const ks_results* r) { return r->algbytes; }
+
+// --- the static feasibility matrix (ks_feas.hip, ks_feas_host.cpp) -----------------------------
+
+// A problem without a device: the encoded host model alone.  Only the host-side entries work on it
+// (ks_problem_static_feasibility with where = 1, ks_problem_save); ks_solve fails with KS_ERR_HIP.
+int ks_problem_create_host(const char* json, size_t len, ks_problem** out) {
+  API_TRY
+  if (!json || !out) throw KsError(KS_ERR_ARG, "null argument");
+  ksjson::Value root = ksjson::Parser(json, len ? len : strlen(json)).parse();
+  std::unique_ptr<ks_problem> pb(new ks_problem());
+  pb->host.build(root);
+  ksjson::release_async(std::move(root));
+  *out = pb.release();
+  return KS_OK;
+  API_CATCH
+}
+
+}  // extern "C"
+
+struct ks_feasibility {
+  ks_problem* pb = nullptr;  // holds a reference: the meta document renders from the host model
+  StaticFeas a;
+  int where = 0;
+  double tpl_ms = 0, node_ms = 0;
+  int64_t bytes_read = 0, bytes_written = 0;
+  ~ks_feasibility() { ks_problem_free(pb); }
+};
+
+namespace {
+struct DevBuf {  // one hipMalloc, freed on every way out
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+struct Events {
+  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  ~Events() {
+    for (auto x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
+void static_feasibility_device(ks_problem* pb, const ks_solve_opts* opts, ks_feasibility& f) {
+  if (pb->device < 0 || !pb->dbuf) throw KsError(KS_ERR_ARG, "the problem was created without a device (where must be 1)");
+  DeviceGuard guard(pb->device, opts);
+  const KsDims& d = pb->dev.d;
+  StaticFeas& a = f.a;
+  a.S = d.S;
+  a.NTPL = d.NTPL;
+  a.N = d.N;
+  a.TW = d.TW;
+  a.NWN = (d.N + 31) / 32;
+  if (static_templates_lds(d) > 60 * 1024) throw KsError(KS_ERR_CAPACITY, "requirement records too wide for the template kernel's LDS");
+  const std::vector<int32_t> sp = state_pods(pb->host);
+  Arena ar;
+  const size_t nrow = (size_t)a.S * a.NTPL;
+  const size_t o_sp = ar.add(std::max<size_t>(sp.size() * 4, 16));
+  const size_t o_code = ar.add(std::max<size_t>(nrow * 4, 16));
+  const size_t o_cnt = ar.add(std::max<size_t>(nrow * 4, 16));
+  const size_t o_opt = ar.add(std::max<size_t>(nrow * a.TW * 4, 16));
+  const size_t o_nb = ar.add(std::max<size_t>((size_t)a.S * a.NWN * 4, 16));
+  const size_t o_nc = ar.add(std::max<size_t>((size_t)a.S * 4, 16));
+  DevBuf buf;
+  HIPCHK(hipMalloc(&buf.p, ar.total));
+  char* b = (char*)buf.p;
+  // every output word is pre-filled with 0xA5 bytes (a word a kernel fails to store reads back as the fill);
+  // node_count is accumulated by atomic adds and starts at zero
+  HIPCHK(hipMemsetAsync(b, 0xA5, ar.total, pb->stream));
+  HIPCHK(hipMemsetAsync(b + o_nc, 0, std::max<size_t>((size_t)a.S * 4, 16), pb->stream));
+  HIPCHK(hipMemcpyAsync(b + o_sp, sp.data(), sp.size() * 4, hipMemcpyHostToDevice, pb->stream));
+  StaticFeasDev o{(const int32_t*)(b + o_sp), (uint32_t*)(b + o_code), (int32_t*)(b + o_cnt), (uint32_t*)(b + o_opt),
+                  (uint32_t*)(b + o_nb), (int32_t*)(b + o_nc)};
+  Events ev;
+  for (auto& e : ev.e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ev.e[0], pb->stream));
+  launch_static_templates(pb->dev, o, pb->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev.e[1], pb->stream));
+  launch_static_nodes(pb->dev, o, pb->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev.e[2], pb->stream));
+  dl(a.tpl_code, o.tpl_code, nrow, pb->stream);
+  dl(a.tpl_count, o.tpl_count, nrow, pb->stream);
+  dl(a.tpl_options, o.tpl_options, nrow * a.TW, pb->stream);
+  dl(a.node_bits, o.node_bits, (size_t)a.S * a.NWN, pb->stream);
+  dl(a.node_count, o.node_count, (size_t)a.S, pb->stream);
+  HIPCHK(hipStreamSynchronize(pb->stream));
+  float t0 = 0, t1 = 0;
+  HIPCHK(hipEventElapsedTime(&t0, ev.e[0], ev.e[1]));
+  HIPCHK(hipEventElapsedTime(&t1, ev.e[1], ev.e[2]));
+  f.tpl_ms = t0;
+  f.node_ms = t1;
+}
+}  // namespace
+
+extern "C" {
+
+int ks_problem_static_feasibility(ks_problem* pb, const ks_solve_opts* opts, int where, ks_feasibility** out) {
+  API_TRY
+  if (!pb || !out) throw KsError(KS_ERR_ARG, "null argument");
+  if (where != 0 && where != 1) throw KsError(KS_ERR_ARG, "where must be 0 (device) or 1 (host)");
+  if (pb->host.dims.negReq)
+    throw KsError(KS_ERR_UNSUPPORTED, "a pod or daemon request is negative: Fits is not monotone and the static bound does not hold");
+  std::unique_ptr<ks_feasibility> f(new ks_feasibility());
+  f->where = where;
+  if (where == 1) static_feasibility_host(pb->host, f->a);
+  else static_feasibility_device(pb, opts, *f);
+  static_feasibility_bytes(pb->host, f->a, &f->bytes_read, &f->bytes_written);
+  pb->refs++;
+  f->pb = pb;
+  *out = f.release();
+  return KS_OK;
+  API_CATCH
+}
+
+void ks_feasibility_free(ks_feasibility* f) { delete f; }
+
+int ks_feasibility_meta(const ks_feasibility* f, char** meta_json) {
+  API_TRY
+  if (!f || !meta_json) throw KsError(KS_ERR_ARG, "null argument");
+  const Host& h = f->pb->host;
+  const auto& t = h.tab;
+  const KsDims& d = h.dims;
+  const StaticFeas& a = f->a;
+  std::string o = "{";
+  auto kv = [&](const char* k, long long v) { o += std::string(o.size() > 1 ? "," : "") + "\"" + k + "\":" + std::to_string(v); };
+  kv("S", a.S); kv("NTPL", a.NTPL); kv("N", a.N); kv("TW", a.TW); kv("NWN", a.NWN); kv("volAny", d.volAny);
+  auto ints = [&](const char* k, size_t cnt, auto&& at) {
+    o += std::string(",\"") + k + "\":[";
+    for (size_t i = 0; i < cnt; i++) o += (i ? "," : "") + std::to_string(at(i));
+    o += "]";
+  };
+  ints("podState0", (size_t)d.P, [&](size_t i) { return (long long)t.pod_state0[i]; });
+  ints("podNState", (size_t)d.P, [&](size_t i) { return (long long)t.pod_nstate[i]; });
+  const std::vector<int32_t> sp = state_pods(h);
+  ints("statePod", (size_t)d.S, [&](size_t s) { return (long long)sp[s]; });
+  o += ",\"templates\":[";
+  for (int tt = 0; tt < d.NTPL; tt++) {
+    const int tb = t.tpl_it_beg[(size_t)tt], cnt = t.tpl_it_beg[(size_t)tt + 1] - tb;
+    o += tt ? ",{\"nodePool\":" : "{\"nodePool\":";
+    ksjson::quote(o, h.tpls[(size_t)tt].pool);
+    o += ",\"instanceTypes\":[";
+    for (int p = 0; p < cnt; p++) {
+      if (p) o += ",";
+      ksjson::quote(o, h.its[(size_t)t.tpl_its[(size_t)(tb + p)]].name);
+    }
+    o += "]}";
+  }
+  o += "],\"nodes\":[";
+  for (int i = 0; i < d.N; i++) {
+    if (i) o += ",";
+    ksjson::quote(o, h.nodes[(size_t)i].name);
+  }
+  o += "],\"ignores\":[\"topology\",\"volumeLimits\"],\"topologyStates\":[";
+  bool first = true;
+  for (int s = 0; s < d.S && d.G > 0; s++) {
+    bool own = false;
+    for (int w = 0; w < d.GMW; w++) own = own || t.st_gown[(size_t)s * d.GMW + w] != 0;
+    if (!own) continue;
+    o += (first ? "" : ",") + std::to_string(s);
+    first = false;
+  }
+  // States whose clear bits hold for a fresh target only: Compatible denies a key the target does not define
+  // unless the operator is NotIn / DoesNotExist (requirements.go:163-174), and a target gains keys as pods land
+  // on it -- a pod with NotIn on a custom label defines it, after which a pod with In on it is compatible.
+  o += "],\"undefinedKeyStates\":[";
+  first = true;
+  for (int s = 0; s < d.S; s++) {
+    const uint32_t* X = &t.st_rs[(size_t)s * d.RSW];
+    uint64_t pos = 0;  // keys the state names with In / Exists (Gt / Lt included)
+    for (uint64_t m = rs_present(X); m; m &= m - 1)
+      if (!op_neg(rs_op(h.L, X, __builtin_ctzll(m)))) pos |= m & (~m + 1);
+    bool undef = false;
+    for (int tt = 0; tt < d.NTPL && !undef; tt++) undef = (pos & ~d.allowWK & ~rs_present(&t.tpl_rs[(size_t)tt * d.RSW])) != 0;
+    for (int n = 0; n < d.N && !undef; n++) undef = (pos & ~rs_present(&t.n_rs0[(size_t)n * d.RSW])) != 0;
+    if (!undef) continue;
+    o += (first ? "" : ",") + std::to_string(s);
+    first = false;
+  }
+  o += "],\"codes\":{";
+  const std::pair<const char*, unsigned> codes[] = {
+      {"FC_NONE", FC_NONE}, {"FC_LIMITS", FC_LIMITS}, {"FC_TAINTS", FC_TAINTS}, {"FC_COMPAT", FC_COMPAT}, {"FC_NO_IT", FC_NO_IT},
+      {"FF_REQ", FF_REQ}, {"FF_FITS", FF_FITS}, {"FF_OFF", FF_OFF}, {"FF_REQ_FITS", FF_REQ_FITS}, {"FF_REQ_OFF", FF_REQ_OFF},
+      {"FF_FITS_OFF", FF_FITS_OFF}};
+  for (size_t i = 0; i < sizeof(codes) / sizeof(codes[0]); i++)
+    o += std::string(i ? ",\"" : "\"") + codes[i].first + "\":" + std::to_string(codes[i].second);
+  o += "}}";
+  *meta_json = strdup(o.c_str());
+  return KS_OK;
+  API_CATCH
+}
+
+int ks_feasibility_template_row(const ks_feasibility* f, int state, int tpl, uint32_t* code, int32_t* count,
+                                const uint32_t** words, int* n_words) {
+  API_TRY
+  if (!f) throw KsError(KS_ERR_ARG, "null argument");
+  const StaticFeas& a = f->a;
+  if (state < 0 || state >= a.S) throw KsError(KS_ERR_ARG, "state out of range");
+  if (tpl < 0 || tpl >= a.NTPL) throw KsError(KS_ERR_ARG, "template out of range");
+  const size_t row = (size_t)state * a.NTPL + tpl;
+  if (code) *code = a.tpl_code[row];
+  if (count) *count = a.tpl_count[row];
+  if (words) *words = a.tpl_options.data() + row * a.TW;
+  if (n_words) *n_words = a.TW;
+  return KS_OK;
+  API_CATCH
+}
+
+int ks_feasibility_node_row(const ks_feasibility* f, int state, int32_t* count, const uint32_t** words, int* n_words) {
+  API_TRY
+  if (!f) throw KsError(KS_ERR_ARG, "null argument");
+  const StaticFeas& a = f->a;
+  if (state < 0 || state >= a.S) throw KsError(KS_ERR_ARG, "state out of range");
+  if (count) *count = a.node_count[(size_t)state];
+  if (words) *words = a.node_bits.data() + (size_t)state * a.NWN;
+  if (n_words) *n_words = a.NWN;
+  return KS_OK;
+  API_CATCH
+}
+
+int ks_feasibility_timing(const ks_feasibility* f, double* kernel_ms, int64_t* bytes_read, int64_t* bytes_written) {
+  API_TRY
+  if (!f) throw KsError(KS_ERR_ARG, "null argument");
+  if (kernel_ms) *kernel_ms = f->tpl_ms + f->node_ms;
+  if (bytes_read) *bytes_read = f->bytes_read;
+  if (bytes_written) *bytes_written = f->bytes_written;
+  return KS_OK;
+  API_CATCH
+}
+
+int ks_feasibility_kernel_times(const ks_feasibility* f, double* templates_ms, double* nodes_ms) {
+  API_TRY
+  if (!f) throw KsError(KS_ERR_ARG, "null argument");
+  if (templates_ms) *templates_ms = f->tpl_ms;
+  if (nodes_ms) *nodes_ms = f->node_ms;
+  return KS_OK;
+  API_CATCH
+}
+
+int ks_feasibility_arrays(const ks_feasibility* f, int dims[5], const uint32_t** tpl_code, const int32_t** tpl_count,
+                          const uint32_t** tpl_options, const uint32_t** node_bits, const int32_t** node_count) {
+  API_TRY
+  if (!f) throw KsError(KS_ERR_ARG, "null argument");
+  const StaticFeas& a = f->a;
+  if (dims) {
+    dims[0] = a.S; dims[1] = a.NTPL; dims[2] = a.N; dims[3] = a.TW; dims[4] = a.NWN;
+  }
+  if (tpl_code) *tpl_code = a.tpl_code.data();
+  if (tpl_count) *tpl_count = a.tpl_count.data();
+  if (tpl_options) *tpl_options = a.tpl_options.data();
+  if (node_bits) *node_bits = a.node_bits.data();
+  if (node_count) *node_count = a.node_count.data();
+  return KS_OK;
+  API_CATCH
+}
 
 }  // extern "C"

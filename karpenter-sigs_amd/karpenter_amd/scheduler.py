@@ -366,13 +366,67 @@ def check_binary(blob):
     _check(lib().ks_problem_check_binary(blob, len(blob)))
 
 
+class StaticFeasibility:
+    """The static feasibility matrix (ks_problem_static_feasibility): numpy arrays tpl_code[S, NTPL],
+    tpl_count[S, NTPL], tpl_options[S, NTPL, TW], node_bits[S, NWN], node_count[S], the meta document that
+    indexes them, and the timing (kernel_ms, templates_ms, nodes_ms, bytes_read, bytes_written).  A clear bit
+    holds for every Solve of the problem; a set one is exact for an empty scheduler without topology and volume
+    limits (meta["ignores"])."""
+
+    def __init__(self, meta, arrays, timing):
+        self.meta = meta
+        self.tpl_code, self.tpl_count, self.tpl_options, self.node_bits, self.node_count = arrays
+        self.kernel_ms, self.templates_ms, self.nodes_ms, self.bytes_read, self.bytes_written = timing
+        self.codes = meta["codes"]
+
+    def state(self, pod, state=0):
+        """The row index of `pod`'s relaxation state number `state` (0: unrelaxed)."""
+        if not 0 <= pod < len(self.meta["podState0"]) or not 0 <= state < self.meta["podNState"][pod]:
+            raise IndexError("pod %d has no relaxation state %d" % (pod, state))
+        return self.meta["podState0"][pod] + state
+
+    def states(self, pod):
+        s0 = self.state(pod, 0)
+        return range(s0, s0 + self.meta["podNState"][pod])
+
+    def options(self, pod, state, tpl):
+        """Names of the instance types a fresh NodeClaim of template `tpl` keeps for the pod in that state."""
+        names = self.meta["templates"][tpl]["instanceTypes"]
+        words = self.tpl_options[self.state(pod, state), tpl]
+        return [n for q, n in enumerate(names) if (int(words[q >> 5]) >> (q & 31)) & 1]
+
+    def nodes(self, pod, state):
+        """Names of the existing nodes that accept the pod in that state."""
+        words = self.node_bits[self.state(pod, state)]
+        return [n for i, n in enumerate(self.meta["nodes"]) if (int(words[i >> 5]) >> (i & 31)) & 1]
+
+    def unschedulable(self):
+        """{pod: [code per template, of its last state]} for the pods with no option and no node in any state of
+        their chain: no Solve of this problem schedules them.  Pods with a state in meta["undefinedKeyStates"] are
+        left out: their clear bits hold for a fresh NodeClaim or an untouched node only (a target gains label keys
+        as other pods land on it)."""
+        out = {}
+        soft = set(self.meta["undefinedKeyStates"])
+        for pod in range(len(self.meta["podState0"])):
+            ss = self.states(pod)
+            if soft.intersection(ss):
+                continue
+            if not any(self.tpl_count[s].any() or self.node_count[s] for s in ss):
+                out[pod] = [int(c) for c in self.tpl_code[ss[-1]]]
+        return out
+
+
 class Scheduler:
     """NewScheduler(...) on the GPU: the snapshot is encoded once and stays resident in HBM.
     Scheduler.from_binary(blob) rebuilds one from save()'s binary snapshot (no JSON parse, no encode)."""
 
-    def __init__(self, snapshot, _binary=None):
+    def __init__(self, snapshot, _binary=None, _host_only=False):
         h = ctypes.c_void_p()
-        if _binary is not None:
+        if _host_only:
+            b = _encode(snapshot)
+            lib().ks_problem_create_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+            _check(lib().ks_problem_create_host(b, len(b), ctypes.byref(h)))
+        elif _binary is not None:
             _check(lib().ks_problem_create_binary(_binary, len(_binary), ctypes.byref(h)))
         else:
             b = _encode(snapshot)
@@ -383,9 +437,58 @@ class Scheduler:
     def from_binary(cls, blob):
         return cls(None, _binary=bytes(blob))
 
+    @classmethod
+    def host_only(cls, snapshot):
+        """The encoded problem without a device (ks_problem_create_host): static_feasibility(where="host") and
+        save() work on it, solve() raises KS_ERR_HIP."""
+        return cls(snapshot, _host_only=True)
+
     def save(self):
         """The binary snapshot of the encoded problem (bytes)."""
         return _take_bytes(lib().ks_problem_save, self._h)
+
+    def static_feasibility(self, where="device", device=-1):
+        """Every relaxation state against every template's instance types and every existing node, from the
+        static tables alone (ks_problem_static_feasibility): a StaticFeasibility.  where="device" runs the two
+        kernels, where="host" the same definitions in plain loops on the host."""
+        import numpy as np
+
+        if where not in ("device", "host"):
+            raise KsError(-6, 'where must be "device" or "host"')
+        l = lib()
+        vp, c = ctypes.c_void_p, ctypes
+        l.ks_problem_static_feasibility.argtypes = [vp, c.POINTER(_Opts), c.c_int, c.POINTER(vp)]
+        l.ks_feasibility_free.argtypes = [vp]
+        l.ks_feasibility_meta.argtypes = [vp, c.POINTER(vp)]
+        l.ks_feasibility_arrays.argtypes = [vp, c.POINTER(c.c_int), c.POINTER(vp), c.POINTER(vp), c.POINTER(vp),
+                                            c.POINTER(vp), c.POINTER(vp)]
+        l.ks_feasibility_timing.argtypes = [vp, c.POINTER(c.c_double), c.POINTER(c.c_int64), c.POINTER(c.c_int64)]
+        l.ks_feasibility_kernel_times.argtypes = [vp, c.POINTER(c.c_double), c.POINTER(c.c_double)]
+        o = _Opts(device, 1, 1, 0, 0)
+        f = vp()
+        _check(l.ks_problem_static_feasibility(self._h, c.byref(o), 1 if where == "host" else 0, c.byref(f)))
+        try:
+            meta = vp()
+            _check(l.ks_feasibility_meta(f, c.byref(meta)))
+            meta = json.loads(_take_str(meta))
+            dims = (c.c_int * 5)()
+            ptr = [vp() for _ in range(5)]
+            _check(l.ks_feasibility_arrays(f, dims, *[c.byref(x) for x in ptr]))
+            S, NTPL, _, TW, NWN = list(dims)
+            shapes = [((S, NTPL), np.uint32), ((S, NTPL), np.int32), ((S, NTPL, TW), np.uint32), ((S, NWN), np.uint32),
+                      ((S,), np.int32)]
+            arrays = []
+            for x, (shape, dt) in zip(ptr, shapes):
+                n = int(np.prod(shape))
+                raw = c.string_at(x, n * 4) if n else b""
+                arrays.append(np.frombuffer(raw, dtype=dt).reshape(shape).copy())
+            ms, tms, nms = c.c_double(), c.c_double(), c.c_double()
+            br, bw = c.c_int64(), c.c_int64()
+            _check(l.ks_feasibility_timing(f, c.byref(ms), c.byref(br), c.byref(bw)))
+            _check(l.ks_feasibility_kernel_times(f, c.byref(tms), c.byref(nms)))
+            return StaticFeasibility(meta, arrays, (ms.value, tms.value, nms.value, br.value, bw.value))
+        finally:
+            l.ks_feasibility_free(f)
 
     def feasibility_rows(self, which):
         """Test / diagnostic read-back (ks_problem_feasibility_rows): which = 0 the pod-state x instance-type

@@ -15,7 +15,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "karpenter-sigs_amd", "build")
 LLVM = "/opt/rocm/lib/llvm/bin"
-TUS = ["ks_solve", "ks_solve_topo", "ks_sim", "ks_sim_topo", "ks_queue"]
+TUS = ["ks_solve", "ks_solve_topo", "ks_sim", "ks_sim_topo", "ks_queue", "ks_feas"]
 FIELDS = [".sgpr_count", ".sgpr_spill_count", ".vgpr_count", ".agpr_count", ".vgpr_spill_count",
           ".private_segment_fixed_size", ".group_segment_fixed_size"]
 
