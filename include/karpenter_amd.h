@@ -73,7 +73,10 @@ int ks_problem_check_binary(const void* buf, size_t len);
  * some negative request), "plans" (the LDS plan at the default and a few reduced budgets), "widePlans" (per budget of "plans", the two
  * plans ks_solve re-plans to when a Solve outgrows the plan's NodeClaim capacity "KO"), "FNR" (relaxation
  * states with label requirements: the rows of k_feasibility_nodes), "keyValues" (per key of "keyNames", the
- * size of its value universe) and "coveredKeys" (the keys k_feasibility's rows decide).
+ * size of its value universe) and "coveredKeys" (the keys k_feasibility's rows decide).  Topology: "tgCntWords"
+ * (count words), "tgSmall" (the prefix of small-key groups), "TK" and "topologyKeys" (the distinct topology keys in
+ * key-slot order), "topologyGroups" ([key slot, domains, in the small prefix, type, hostname] per group); each plan
+ * has "tcl" / "tdl" (count words / node-domain words it keeps in LDS).
  * Diagnostics / CPU tests. */
 int ks_problem_inspect(const char* snapshot_json, size_t len, char** dims_json);
 
@@ -271,7 +274,8 @@ int ks_cons_create(const char* snapshot_json, size_t len, ks_cons** out);
 int ks_cons_save(const ks_cons* c, void** buf, size_t* len);
 int ks_cons_create_binary(const void* buf, size_t len, ks_cons** out);
 /* Host-only (no device): JSON {candidates:[{name, disruptionCost, pods}], sims, multiPrefixes, recordBytes,
- * R, G, lean, negReq, simPlan:{KO, KL, talloc, tsort, lds}} (simPlan: the LDS plan of a world-1 pass). */
+ * R, G, lean, negReq, simPlan:{KO, KL, talloc, tsort, tcl, tdl, lds}} (simPlan: the LDS plan of a world-1 pass)
+ * plus tgSmall, tgCntWords, TK, topologyKeys and topologyGroups as ks_problem_inspect reports them. */
 int ks_cons_inspect(const char* snapshot_json, size_t len, char** out_json);
 /* Cluster-state events between two passes against the resident handle (replaces re-reading the cluster
  * and rebuilding the scheduler per pass: state/cluster.go:220-512 UpdatePod/DeletePod/DeleteNode,

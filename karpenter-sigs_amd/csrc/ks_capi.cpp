@@ -1201,6 +1201,7 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   kv("volAny", d.volAny); kv("volDrivers", d.VD); kv("volPvcs", d.NVU); kv("volLogCap", d.vLogCap);
   kv("volSharedPods", nshared); kv("volErrorPods", nverr); kv("injectFailed", nfail);
   kv("volStaticMounts", (long long)(h.tab.pod_vsbeg.empty() ? 0 : h.tab.pod_vsbeg.back()));
+  o += "," + topo_inspect_json(h);  // the count table's split, the key slots and each group's (slot, nv, small, type, host)
   // LDS plans (ks_solve.hip make_plan) at the default and a few reduced budgets
   // the templates' Pareto fronts (pareto_fronts): positions per template, [] where a template is not pruned
   std::vector<int32_t> frontBeg, frontPos;
@@ -1226,7 +1227,8 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
     Plan pl = make_plan(pd, budget, false, wide, (int)frontPos.size());
     return "{\"KO\":" + std::to_string(pl.KO) +
            ",\"KL\":" + std::to_string(pl.KL) + ",\"talloc\":" + std::to_string(pl.talloc) +
-           ",\"tsort\":" + std::to_string(pl.tsort) + ",\"tmask\":" + std::to_string(pl.tmask) +
+           ",\"tsort\":" + std::to_string(pl.tsort) + ",\"tcl\":" + std::to_string(pl.tcl) +
+           ",\"tdl\":" + std::to_string(pl.tdl) + ",\"tmask\":" + std::to_string(pl.tmask) +
            ",\"tmaskBytes\":" + std::to_string(pl.tmask ? tpl_mask_bytes(d.NTPL, d.TW) : 0) + ",\"lds\":" + std::to_string(pl.lds) + "}";
   };
   for (size_t i = 0; i < sizeof(budgets) / sizeof(budgets[0]); i++)

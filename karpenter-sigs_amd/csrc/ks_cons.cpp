@@ -2585,7 +2585,8 @@ std::string inspect_json(const ks_cons& c, bool nodes) {
   o += ",\"R\":" + std::to_string(h.dims.R) + ",\"G\":" + std::to_string(h.dims.G) + ",\"lean\":" +
        std::to_string(h.dims.lean) + ",\"negReq\":" + std::to_string(h.dims.negReq) + ",\"simPlan\":{\"KO\":" +
        std::to_string(pl.KO) + ",\"KL\":" + std::to_string(pl.KL) + ",\"talloc\":" + std::to_string(pl.talloc) +
-       ",\"tsort\":" + std::to_string(pl.tsort) + ",\"lds\":" + std::to_string(pl.lds) + "}";
+       ",\"tsort\":" + std::to_string(pl.tsort) + ",\"tcl\":" + std::to_string(pl.tcl) + ",\"tdl\":" +
+       std::to_string(pl.tdl) + ",\"lds\":" + std::to_string(pl.lds) + "}," + topo_inspect_json(h);
   o += ",\"sims\":" + std::to_string(c.sims.size()) + ",\"multiPrefixes\":" + std::to_string(c.multiHi) +
        ",\"recordBytes\":" + std::to_string(4 * c.recWords) + ",\"pods\":" + std::to_string(h.dims.P) +
        ",\"nodes\":" + std::to_string(h.dims.N) + ",\"groups\":" + std::to_string(h.dims.G) +

@@ -686,11 +686,16 @@ void Host::build(const Value& root) {
   // requirements.go:163-174) reads the node's value of a key only when the pod names it, the daemon overhead
   // test likewise, and a node's record is never rendered.  So the label keys only nodes carry (a production
   // node has dozens) do not count against the 64-key universe and cost no record words.
-  for (auto& n : nodes)
-    for (auto& kv : n.labels) {
+  // The label-only nodes of the cluster's bound pods (clusterNodes) likewise: countDomains tests a spread group's
+  // node filter against their labels (addNodeLabels), so their values of those keys (a hostname label, say) need ids.
+  auto internKnown = [&](const std::map<std::string, std::string>& labels) {
+    for (auto& kv : labels) {
       const std::string k = normalize_key(kv.first);
       if (keyId.count(k)) intern(k, kv.second);
     }
+  };
+  for (auto& n : nodes) internKnown(n.labels);
+  for (auto& nl : nodeLabelsByName) internKnown(nl.second);
   for (auto& kv : valueSet_[kHostname])
     if (kv.rfind("hostname-placeholder-", 0) == 0)
       throw KsError(-2, "input names a hostname-placeholder value (reserved for new NodeClaims)");

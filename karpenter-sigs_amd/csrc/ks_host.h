@@ -277,6 +277,10 @@ constexpr int kFrontMax = 64;
 void pareto_fronts(const KsDims& dims, const std::vector<int32_t>& tpl_it_beg, const std::vector<int32_t>& tpl_its,
                    const std::vector<int64_t>& it_alloc, std::vector<int32_t>& beg, std::vector<int32_t>& pos);
 
+// The topology tables' shape for the inspectors (ks_topo.cpp), as JSON members without braces: tgSmall, tgCntWords,
+// TK, topologyKeys (key names in key-slot order) and topologyGroups ([slot, nv, small, type, host] per group).
+std::string topo_inspect_json(const Host& h);
+
 struct ArOut;
 struct ArIn;
 void host_save(ArOut& a, Host& h);

@@ -630,4 +630,28 @@ bool Host::topoClusterPod(const PodH& cp, std::vector<std::pair<int, int>>& cont
   return true;
 }
 
+// Read from the device tables' host images alone (tg_meta), so a handle loaded from a binary snapshot reports the
+// same.  A group is in the small prefix when its count words start below tgSmall.
+std::string topo_inspect_json(const Host& h) {
+  const KsDims& d = h.dims;
+  std::string o = "\"tgSmall\":" + std::to_string(d.tgSmall) + ",\"tgCntWords\":" + std::to_string(d.tgCntWords) +
+                  ",\"TK\":" + std::to_string(d.TK) + ",\"topologyKeys\":[";
+  std::vector<int> slotKey((size_t)std::max(d.TK, 0), -1);
+  for (int g = 0; g < d.G; g++) {
+    const int32_t* m = &h.tab.tg_meta[(size_t)g * TGM_WORDS];
+    if (m[TGM_KSLOT] >= 0 && m[TGM_KSLOT] < d.TK) slotKey[(size_t)m[TGM_KSLOT]] = m[TGM_KEY];
+  }
+  for (size_t k = 0; k < slotKey.size(); k++) {
+    if (k) o += ",";
+    ksjson::quote(o, slotKey[k] >= 0 ? h.keyNames[(size_t)slotKey[k]] : std::string());
+  }
+  o += "],\"topologyGroups\":[";
+  for (int g = 0; g < d.G; g++) {
+    const int32_t* m = &h.tab.tg_meta[(size_t)g * TGM_WORDS];
+    o += std::string(g ? ",[" : "[") + std::to_string(m[TGM_KSLOT]) + "," + std::to_string(m[TGM_NV]) + "," +
+         (m[TGM_CNT] < d.tgSmall ? "1," : "0,") + std::to_string(m[TGM_TYPE]) + "," + std::to_string(m[TGM_HOST]) + "]";
+  }
+  return o + "]";
+}
+
 }  // namespace ks
