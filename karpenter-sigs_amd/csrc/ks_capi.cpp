@@ -1209,7 +1209,9 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   o += ",\"runFuse\":" + std::to_string(run_fuse_build()) + ",\"sortLeaf\":" + std::to_string(sort_leaf_build()) +
        ",\"closedShift\":" + std::to_string(closed_shift_build()) + ",\"tplMasks\":" + std::to_string(tpl_masks_build()) +
        ",\"logRuns\":" + std::to_string(log_runs_build()) + ",\"sortRegs\":" + std::to_string(sort_regs_build()) +
-       ",\"sortRegsN64\":" + std::to_string(sort_regs_n64_build()) + ",\"queuePacked\":" + std::to_string(queue_packed_build()) + ",\"paretoFronts\":[";
+       ",\"sortRegsN64\":" + std::to_string(sort_regs_n64_build()) + ",\"queuePacked\":" + std::to_string(queue_packed_build()) +
+       ",\"capBound\":" + std::to_string(cap_bound_build()) + ",\"thrBatch\":" + std::to_string(thr_batch_build()) +
+       ",\"runChain\":" + std::to_string(run_chain_build()) + ",\"paretoFronts\":[";
   for (int t = 0; t < d.NTPL; t++) {
     o += t ? ",[" : "[";
     for (int i = frontBeg[(size_t)t]; i < frontBeg[(size_t)t + 1]; i++)
@@ -1644,7 +1646,10 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "cycTplMax", "runCapFront", "runCapFull", "runCrossClosed", "runMoves",
                                 "cycSortExactLe12", "cycSortExactLt50", "cycSortExactGe50", "closedShiftDiff",
                                 "tplMaskFills", "tplMaskHits", "runRecs", "sortsRegs", "sortRegsBail", "sortRegsOver",
-                                "cycTplCand", "cycTplFeas", "cycTplFilter", "cycTplThr", "cycLogLoad", "cycLogStore"};
+                                "cycTplCand", "cycTplFeas", "cycTplFilter", "cycTplThr", "cycLogLoad", "cycLogStore",
+                                "capBoundSkips", "thrBatchCalls", "thrMultiChunk", "chainPods",
+                                "cycStepOpen", "cycStepRun", "cycStepSingle", "stepsOpen", "stepsRun", "stepsSingle",
+                                "thrMoves", "cycThrMove", "runCapZero"};
   static_assert(sizeof(names) / sizeof(names[0]) == CT_NCOUNTERS, "one name per counter");
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);
   // the launched k_solve instantiation: the last launch's fields, and every launch of this Solve in order

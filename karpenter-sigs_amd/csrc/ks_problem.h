@@ -364,9 +364,21 @@ enum Counter {
   // the window (waited for), its log_batch calls or its record
   CT_CYC_SPLIT,
   CT_CYC_SPLIT_END = CT_CYC_SPLIT + 6,
-  CT_NCOUNTERS = CT_CYC_SPLIT_END
+  CT_CAP_BOUND_SKIPS = CT_CYC_SPLIT_END,  // LEAN Solve: runs whose capacity the stored headroom showed to be 0, so that
+                                          // claim_run_cap was not called (KS_CAP_BOUND)
+  CT_THR_BATCH_CALLS,  // LEAN Solve: claim_full calls that advanced thresholds through the batched first chunk (KS_THR_BATCH)
+  CT_THR_MULTI_CHUNK,  // ... and those of them in which one resource dropped more than 64 options
+  CT_CHAIN_PODS,       // LEAN Solve: popped pods that skipped the node phase behind an identical pod a NodeClaim took
+                       // (KS_RUN_CHAIN; `pops` counts them, `runPods` does not)
+  // diagnostic build: the LEAN Solve's main-loop steps by kind, cycles [3] then counts [3] (a step that opens a
+  // NodeClaim, one that places a run of k > 0 further pods, a single pod); claim_full calls that moved a threshold and
+  // the cycles of their advance (inside cycFullThr); claim_run_cap calls that returned 0
+  CT_KIND,
+  CT_KIND_END = CT_KIND + 9,
+  CT_NCOUNTERS = CT_KIND_END
 };
 enum SplitSub { YS_TPL_CAND = 0, YS_TPL_FEAS, YS_TPL_FILTER, YS_TPL_THR, YS_LOG_LOAD, YS_LOG_STORE };
+enum KindSub { KD_CYC_OPEN = 0, KD_CYC_RUN, KD_CYC_SINGLE, KD_N_OPEN, KD_N_RUN, KD_N_SINGLE, KD_THR_MOVES, KD_CYC_THR_MOVE, KD_CAP_ZERO };
 
 enum StepSub {
   SS_SORT_FAST = 0,  // re-sorts the wave-parallel partialInsertionSort finished (inside CT_CYC_SORT, as the next two)

@@ -13,9 +13,11 @@
 // 1: one sort pass over a packed key where it fits 64 bits (0: always the chained passes).  A Solve's order is
 // needed once per handle and is not kept across Solves.  Measured on C2 at -0.106 ms of 6.217 and -0.1225 ms of
 // 6.256 in two sessions, every run faster than every run without it, but under the sessions' margins of three
-// spreads, 0.222 and 0.123 ms: off
+// spreads of the whole step, 0.222 and 0.123 ms.  Round 15 judged it where it acts, on the
+// HIP-event time of everything but k_solve: 0.0745 ms against 0.1545 ms per Solve in four alternating pairs, nine
+// times that figure's spread, and the step faster in every pair (-0.074 to -0.116 ms): on
 #ifndef KS_QUEUE_PACKED
-#define KS_QUEUE_PACKED 0
+#define KS_QUEUE_PACKED 1
 #endif
 
 #include <hipcub/hipcub.hpp>

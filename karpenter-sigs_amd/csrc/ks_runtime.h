@@ -35,6 +35,9 @@ int log_runs_build();
 int sort_regs_build();     // KS_SORT_REGS ("sortRegs") and its n <= 64 form, KS_SORT_REGS_N64 ("sortRegsN64")
 int sort_regs_n64_build();
 int queue_packed_build();  // KS_QUEUE_PACKED ("queuePacked", ks_queue.hip)
+int cap_bound_build();     // KS_CAP_BOUND ("capBound"), KS_THR_BATCH ("thrBatch")
+int thr_batch_build();
+int run_chain_build();     // KS_RUN_CHAIN ("runChain")
 // ks_claim_sort_probe's kernel (ks_solve.hip): device pointers, how [64] (how, path); n <= kProbeMaxN, R 3 or 4
 hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,
                             const int64_t* chead, int32_t* ptpl, int64_t* phead, int32_t* how, hipStream_t st);

@@ -105,6 +105,24 @@
 #ifndef KS_LOG_RUNS
 #define KS_LOG_RUNS 1
 #endif
+// LEAN Solve: a pod that exceeds the headroom commit_claim just stored for its claim's position (max Allocatable -
+// requests, the quick test's upper bound for every remaining option) in some resource fits none of them a second
+// time: the run's capacity is 0 without a claim_run_cap call (0: the call is always made)
+#ifndef KS_CAP_BOUND
+#define KS_CAP_BOUND 1
+#endif
+// LEAN Solve: 1 lets claim_full's threshold advance issue the first 64-entry chunk of every resource together (the
+// sorted Allocatables, their positions, the option-bit clears, the ballots) instead of resource after resource; a
+// resource that dropped all 64 goes on in the per-resource loop (0: that loop alone).  Measured on C2 at +0.072 ms
+// of 5.8985 (four runs each, every run slower than every run without it): off
+#ifndef KS_THR_BATCH
+#define KS_THR_BATCH 0
+#endif
+// LEAN Solve: 1 lets a popped pod skip the existing-node phase when the pod before it landed on a NodeClaim and is
+// identical to it by the claim runs' identity (0: every popped pod scans the nodes)
+#ifndef KS_RUN_CHAIN
+#define KS_RUN_CHAIN 0
+#endif
 
 #include "ks_gosort.h"
 #include "ks_problem.h"
@@ -1218,6 +1236,17 @@ struct Solver : ClaimSort {
   LI32 s_fbeg;          // [NTPL+1]
   LI32 s_front;         // [frontTotal] template positions
   mutable int64_t capFront = 0, capFull = 0;  // claim_run_cap calls by path
+  // LEAN Solve (KS_CAP_BOUND): commit_claim notes whether the pod exceeds the headroom it stores in some resource;
+  // the run that would follow then has capacity 0 and claim_run_cap is not called (capBoundSkips)
+  static constexpr bool CAP_BOUND = KS_CAP_BOUND && KS_CLAIM_RUNS && LEAN && !SIM;
+  // LEAN Solve (KS_RUN_CHAIN): a pod identical to the one a NodeClaim just took skips the node phase (ks_solve_body.inc)
+  static constexpr bool RUN_CHAIN = KS_RUN_CHAIN && KS_CLAIM_RUNS && LEAN && !SIM;
+  bool capOver = false;
+  int64_t capBoundSkips = 0;
+  // LEAN Solve (KS_THR_BATCH): claim_full calls whose threshold advance took the batched first chunk, and those of
+  // them in which one resource dropped more than 64 options (the per-resource loop went on)
+  static constexpr bool THR_BATCH = KS_THR_BATCH && LEAN && !SIM;
+  int64_t thrBatchCalls = 0, thrMultiChunk = 0;
   LU32 s_rmv;           // SIM: [ceil(N/32)] nodes removed by the simulation (the candidates)
   LU32 s_tch;           // SIM: [ceil(N/32)] nodes whose requests live in a W.n_req slot
   LU32 s_tchr;          // SIM: [ceil(N/32)] nodes whose requirements live in a W.n_rs slot; Solve (d.fnOn): nodes
@@ -1261,6 +1290,7 @@ struct Solver : ClaimSort {
   mutable uint64_t xcyc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the step's sub-phases (StepSub)
   uint64_t ecyc[3] = {0, 0, 0};  // the exact re-sorts' cycles by size (CT_CYC_EXACT_BY_N)
   mutable uint64_t ycyc[6] = {0, 0, 0, 0, 0, 0};  // SS_TPL_DERIVE and SS_LOG split (SplitSub)
+  mutable uint64_t kcyc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // the steps by kind, threshold moves, empty runs (KindSub)
 #endif
 
   __device__ Solver(const KsDev& D_, const KsWork KS_C& W_, const Plan& p_) : D(D_), d(D_.d), W(W_), pl(p_) {}
@@ -2264,10 +2294,51 @@ struct Solver : ClaimSort {
       }
       copy_words(s_rem, v.rem + (int64_t)c * d.TW, d.TW);
       wsync();
+#ifdef KS_PHASE_STATS
+      const uint64_t tmv = __builtin_amdgcn_s_memtime();
+      kcyc[KD_THR_MOVES] += moves;
+#endif
+      [[maybe_unused]] bool more[RM] = {};  // KS_THR_BATCH: the resource's first chunk dropped all 64 (the loop below goes on from there)
+      if constexpr (THR_BATCH) {
+        // The resources' advances do not depend on each other: the clears commute and an option two resources drop
+        // leaves the count once either way (the wave's LDS operations execute in order).  So the first chunk of every
+        // resource goes out together, three LDS round trips in all instead of three per resource.  A lane with
+        // nothing to drop reads the table's last entry and clears no bit (mask ~0); nIT > 0 here (moves or changed
+        // with an option left).
+        int pos[RM];
+        bool ex[RM];
+        uint32_t old[RM];
+        thrBatchCalls++;
+#pragma unroll
+        for (int r = 0; r < RM; r++) {
+          if (RT == 0 && r >= d.R) break;
+          const int i = nthr[r] + lane(), ii = i < nIT ? i : (nIT > 0 ? nIT - 1 : 0);
+          const int64_t base = (int64_t)tb * R() + (int64_t)r * nIT;
+          ex[r] = (nxt[r] < req[r]) & (i < nIT) & (tsort_a(base + ii) < req[r]);
+          pos[r] = tsort_p(base + ii);
+        }
+#pragma unroll
+        for (int r = 0; r < RM; r++) {
+          if (RT == 0 && r >= d.R) break;
+          const int q = ex[r] ? pos[r] : 0;
+          old[r] = lds_and(s_rem + (q >> 5), ex[r] ? ~(1u << (q & 31)) : ~0u);
+        }
+#pragma unroll
+        for (int r = 0; r < RM; r++) {
+          if (RT == 0 && r >= d.R) break;
+          const bool was = ex[r] & (((old[r] >> (pos[r] & 31)) & 1u) != 0);
+          const int nm = __popcll(wballot(ex[r]));
+          removed += __popcll(wballot(was));
+          nthr[r] += nm;
+          examined += nm;
+          more[r] = nm == kWave;
+        }
+      }
+      bool multi = false;  // some resource dropped options past its first chunk
       for (int r = 0; r < R(); r++) {
         const int64_t base = (int64_t)tb * R() + (int64_t)r * nIT;
         int k = nthr[r];
-        if (!(nxt[r] < req[r])) continue;
+        if (THR_BATCH ? !more[r] : !(nxt[r] < req[r])) continue;
         while (k < nIT) {
           const int i = k + lane();
           const bool ex = i < nIT && tsort_a(base + i) < req[r];
@@ -2285,10 +2356,15 @@ struct Solver : ClaimSort {
           examined += nm;
           if (nm < kWave) break;
         }
+        if constexpr (THR_BATCH) multi |= k > nthr[r];
         nthr[r] = k;
       }
+      if constexpr (THR_BATCH) thrMultiChunk += multi;
       algbytes += 8 * d.TW + 16 * R() + 4 * R() + (int64_t)examined * 12;
       wsync();
+#ifdef KS_PHASE_STATS
+      if (moves) kcyc[KD_CYC_THR_MOVE] += __builtin_amdgcn_s_memtime() - tmv;
+#endif
       PHS_END(u1, 1);
       if (!changed) {
         ncnt = uni(v.cnt[c]) - removed;
@@ -2423,6 +2499,18 @@ struct Solver : ClaimSort {
       v.req[(int64_t)c * R() + r] = req[r];
       v.thr[(int64_t)c * R() + r] = nthr[r];
       s_phead[(int64_t)pos * R() + r] = heads[r] - pod[r];
+    }
+    if constexpr (CAP_BOUND) {
+      // The headroom now stored bounds Allocatable - requests of every option the claim has left (the quick test
+      // rejects on it).  An identical pod above it in some resource fits none of them: run_cap gives 0 there for
+      // every option, whatever the request (0, 1 or more).  A loose bound only leaves the call to be made.
+      bool over = false;
+#pragma unroll
+      for (int r = 0; r < RM; r++) {
+        if (RT == 0 && r >= d.R) break;
+        over |= pod[r] > heads[r] - pod[r];
+      }
+      capOver = ub(over);
     }
     v.cnt[c] = ncnt;
     s_okey[pos] = okNew;
@@ -3553,6 +3641,9 @@ int sort_leaf_build() { return KS_SORT_LEAF && !KS_SORT_LANE0; }
 int closed_shift_build() { return KS_CLOSED_SHIFT && KS_SORT_CLOSED; }
 int sort_regs_build() { return KS_SORT_REGS != 0 && KS_SORT_OUTLINE; }
 int sort_regs_n64_build() { return sort_regs_build() && KS_SORT_REGS_N64; }
+int cap_bound_build() { return KS_CAP_BOUND && KS_CLAIM_RUNS; }
+int thr_batch_build() { return KS_THR_BATCH; }
+int run_chain_build() { return KS_RUN_CHAIN && KS_CLAIM_RUNS; }
 
 // Test / diagnostic kernel (ks_claim_sort_probe): Solver::sort_claims' logic on arrays of the caller's choosing,
 // one wave, no Solve.  keys / order [n] are loaded into LDS with the position arrays ptpl / phead gathered from the

@@ -59,6 +59,8 @@
     if (pl.tmask)
       for (int i = lane(); i < d.NTPL; i += kWave) S.s_tmv[i] = 0;  // no row filled yet
   }
+  constexpr bool CAPB = Solver<RT, TL, SIM, TOPO, LEAN>::CAP_BOUND;
+  constexpr bool CHAINB = Solver<RT, TL, SIM, TOPO, LEAN>::RUN_CHAIN;
   constexpr bool FRONT = Solver<RT, TL, SIM, TOPO, LEAN>::RUN_FRONT;
   S.s_fbeg = (LI32)take(FRONT ? 4 * (size_t)(d.NTPL + 1) : 0);
   S.s_front = (LI32)take(FRONT ? 4 * (size_t)D.frontTotal : 0);
@@ -304,6 +306,12 @@
   int64_t crossClosed = 0, runMoves = 0;
   int stopC = -1;                    // the claim of a continuation just refused
   int64_t sortB = 0, pendSortB = 0;  // this add()'s re-sort bytes; those of a re-sort run for the next add()
+  // LEAN Solve (KS_RUN_CHAIN): the pod just placed landed on a NodeClaim and the next queue pod is identical to it
+  // (the claim runs' identity): that pod's step skips the node phase.  The identical pod before it failed every
+  // existing node, a LEAN pod has no host ports, volumes or keys, and nodes only change when a pod lands on one:
+  // none did.  nodeAB: the node phase's algorithmic bytes of the last pod that ran it, credited to each chained pod
+  bool chain = false;
+  int64_t nodeAB = 0, chainPods = 0;
   // Every pop either places a pod, relaxes it, or marks it stale; the reference's queue can cycle
   // O(P^2) in adversarial inputs, far beyond any realistic batch.  Bound it so a logic error ends the
   // kernel with KE_ITER_CAP instead of hanging the device.
@@ -551,6 +559,14 @@
     const int64_t abPop = S.algbytes;  // (claim runs: one pod's algorithmic bytes)
     const int prevStop = stopC;        // (claim runs: the claim whose run the step before left to this pod's scan)
     stopC = -1;
+    // KS_RUN_CHAIN: a chained pod is a popped pod (`pops` counts it, `runPods` does not); its run length is kept for
+    // the chain test at the step's end
+    const bool chained = CHAINB && chain;
+    const int rlp = CHAINB ? rdl(w.rl, wi) : 0;
+    if constexpr (CHAINB) {
+      chain = false;
+      chainPods += chained;
+    }
     const int s = rdl(w.s, wi);
     const int sflags = rdl(w.flags, wi);
     const uint64_t toltpl = (uint64_t)rdl64((int64_t)w.toltpl, wi);
@@ -595,12 +611,19 @@
     }
     PH_END(t0, 0);
     bool placed = false;
+    bool onClaim = false;  // KS_RUN_CHAIN: the pod landed on a NodeClaim (claim scan or try_templates) ...
+    int kRun = 0;          // ... and the run that followed placed this many more
+#ifdef KS_PHASE_STATS
+    int skind = KD_CYC_SINGLE;  // the step's kind (KindSub): a single pod unless it opens a NodeClaim or places a run
+#endif
     int rfirst = -1;  // RSK: the first node of this scan passing the resource test (-1: none yet)
     // 1) existing nodes in order (none can pass when a matching group admits no domain)
     PH_BEGIN(t1);
     // (unlabelled nodes choose their domain from their requirements: no shortcut then)
     // (GetVolumes failing for the pod fails ExistingNode.Add on every node, existingnode.go:70-73)
-    const bool skipNodes = (TOPO && S.t_nonode && !d.tgUnlab) || (S.volA() && (pfl & PF_VOLERR));
+    // (KS_RUN_CHAIN: every node failed the identical pod before this one and none changed since)
+    const bool skipNodes = (TOPO && S.t_nonode && !d.tgUnlab) || (S.volA() && (pfl & PF_VOLERR)) || chained;
+    const int64_t abNode = CHAINB ? S.algbytes : 0;
     int scanFrom = 0;
     if constexpr (NW > 0) {
       // (problems with unlabelled nodes scan every node through node_okK, which handles them)
@@ -840,6 +863,10 @@
     if (useLive && !placed) S.algbytes += (int64_t)(d.N - scanFrom) * (16 * R + 16);
     SPHS_END(S, tls, 3);  // stats build: the scan past the window
     PH_END(t1, 1);
+    if constexpr (CHAINB) {  // the skipped node phase counts what it counted for the identical pod that ran it
+      if (chained) S.algbytes += nodeAB;
+      else if (!placed) nodeAB = S.algbytes - abNode;
+    }
     // every node from rskip on was tested (up to the fit, if any): the first passing Fits bounds the prefix
     // (with the live list the scan past the window tested only live nodes: the window's prefix is what is known)
     if (RSK && !skipNodes && d.N > 0) rskip = rfirst >= 0 ? rfirst : useLive ? scanFrom : d.N;
@@ -893,6 +920,7 @@
             srt = U(inl ? S.template commit_claim<true>(c, jj, nclaims, p, sflags, pod, req, nthr, ncnt, nlog)
                          : S.template commit_claim<false>(c, jj, nclaims, p, sflags, pod, req, nthr, ncnt, nlog));
             placed = true;
+            if constexpr (CHAINB) onClaim = true;
             if constexpr (SORTC) dpos = srt ? -1 : jj;
             if constexpr (LEAN && !SIM && KS_CLAIM_RUNS) {
               // the identical pods that follow land here too (claim_run_cap): placed in one step.  While nothing
@@ -934,7 +962,15 @@
                     // the quick test (an upper bound, so a certain reject; those claims did not change in this
                     // step).  One that passes stops it: the array is sorted and the next pod takes its own step.
                     PH_BEGIN(trc);
-                    const int cap = inl ? S.template claim_run_cap<true>(c, pod, m) : S.template claim_run_cap<false>(c, pod, m);
+                    int cap = 0;
+                    if (CAPB && S.capOver) {
+                      S.capBoundSkips++;  // KS_CAP_BOUND: no option takes a second pod
+                    } else {
+                      cap = inl ? S.template claim_run_cap<true>(c, pod, m) : S.template claim_run_cap<false>(c, pod, m);
+#ifdef KS_PHASE_STATS
+                      S.kcyc[KD_CAP_ZERO] += cap == 0;  // (calls made only: a skipped call is capBoundSkips')
+#endif
+                    }
                     SXPH_END(S, trc, SS_RUN_CAP);
                     PH_BEGIN(tcl);
                     int left = m < cap ? m : cap, K = uni(S.s_okey[jj]);
@@ -1141,7 +1177,15 @@
                     const int cj = uni(S.s_okey[jj]);
                     const int nx = jj + 1 < nclaims ? uni(S.s_okey[jj + 1]) : 0x3fffffff;
                     const int M = m < nx - cj + 1 ? m : nx - cj + 1;
-                    k = inl ? S.template claim_run_cap<true>(c, pod, M) : S.template claim_run_cap<false>(c, pod, M);
+                    k = 0;
+                    if (CAPB && S.capOver) {
+                      S.capBoundSkips++;
+                    } else {
+                      k = inl ? S.template claim_run_cap<true>(c, pod, M) : S.template claim_run_cap<false>(c, pod, M);
+#ifdef KS_PHASE_STATS
+                      S.kcyc[KD_CAP_ZERO] += k == 0;
+#endif
+                    }
                     credit = (int64_t)k * (ab0 - abPop);  // each pod scanned as the first one did
                   }
                   if (k > 0) {
@@ -1211,6 +1255,10 @@
                     if (wi > wn) wi = wn;  // the run reached past the window: refill at the loop head
                     runs++;
                     runPods += k;
+                    if constexpr (CHAINB) kRun = k;
+#ifdef KS_PHASE_STATS
+                    skind = KD_CYC_RUN;
+#endif
                   }
                 }
               }
@@ -1239,12 +1287,42 @@
       dpos = -1;  // a descent left here is an appended claim's
       if (r < 0) { err = KE_CLAIM_CAP; break; }
       if (r == 1) placed = true;
+      if constexpr (CHAINB) onClaim = r == 1;
+#ifdef KS_PHASE_STATS
+      if (r == 1) skind = KD_CYC_OPEN;
+#endif
       if (r == 2) {  // no templates: add() returns a nil error
         W.pod_status[p] = ST_SCHEDULED;  // wave-wide store of a uniform value
         placed = true;
       }
     }
     if (U(placed)) {
+      if constexpr (CHAINB) {
+        // Is the next queue pod of this pod's identical-pod run?  The claim runs' identity: while nothing was pushed
+        // back, the popped pod's run length less the pods placed since; otherwise the window's next lane with the same
+        // template tolerations, tolerations and requests, not stale.  (A window that ended: the next pod takes a
+        // whole step.)
+        if (onClaim && qlen > 0) {
+          bool nx = false;
+          if (ident) {
+            nx = rlp - 1 - kRun > 0;
+          } else if (wi < wn) {
+            bool same = lane() == wi && w.toltpl == toltpl && w.tol0 == tol0 && w.tol1 == tol1;
+#pragma unroll
+            for (int r = 0; r < RM; r++) {
+              if (RT == 0 && r >= R) break;
+              same &= w.req[r] == pod[r];
+            }
+            same &= !((uint32_t)(w.ll >> 32) == epoch && (uint32_t)w.ll == (uint32_t)qlen);
+            nx = wballot(same) != 0;
+          }
+          chain = nx;
+        }
+      }
+#ifdef KS_PHASE_STATS
+      S.kcyc[skind] += __builtin_amdgcn_s_memtime() - t0;
+      S.kcyc[skind + KD_N_OPEN] += 1;
+#endif
       // SIM: the epilogue reads the final status; only a pod that failed before needs a store
       if (SIM && rdl(w.st, wi - 1) == ST_FAILED) W.pod_status[p] = ST_SCHEDULED;  // (wave-wide, uniform)
       continue;
@@ -1326,6 +1404,12 @@
       W.counters[CT_SORT_REGS_BAIL] = S.sortRegsBail;
       W.counters[CT_SORT_REGS_OVER] = S.sortRegsOver;
     }
+    if constexpr (CAPB) W.counters[CT_CAP_BOUND_SKIPS] = S.capBoundSkips;
+    if constexpr (CHAINB) W.counters[CT_CHAIN_PODS] = chainPods;
+    if constexpr (decltype(S)::THR_BATCH) {
+      W.counters[CT_THR_BATCH_CALLS] = S.thrBatchCalls;
+      W.counters[CT_THR_MULTI_CHUNK] = S.thrMultiChunk;
+    }
 #ifdef KS_PHASE_STATS
     for (int i = 0; i < 7; i++) W.counters[CT_CYC_POP + i] = (int64_t)cyc[i];
     W.counters[CT_CYC_TOTAL] = (int64_t)(__builtin_amdgcn_s_memtime() - tstart);
@@ -1336,6 +1420,7 @@
     for (int i = 0; i < 3; i++) W.counters[CT_CYC_EXACT_BY_N + i] = (int64_t)S.ecyc[i];
     W.counters[CT_CLOSED_SHIFT_DIFF] = S.shiftDiff;
     for (int i = 0; i < 6; i++) W.counters[CT_CYC_SPLIT + i] = (int64_t)S.ycyc[i];
+    for (int i = 0; i < 9; i++) W.counters[CT_KIND + i] = (int64_t)S.kcyc[i];
 #endif
   }
   if constexpr (SIM) S.sim_record(P, nclaims, hostCtr, allSched, err, !ident, anyRelaxed);

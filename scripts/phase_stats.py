@@ -41,6 +41,17 @@ print("re-sorts with a descent %d: fast %d exact %d closed %d;  n <= 12: %d, 12 
 print("tplMaskFills %s tplMaskHits %s runRecs %s" % (st.get("tplMaskFills"), st.get("tplMaskHits"), st.get("runRecs")))
 print("sortsRegs %s sortRegsOver %s sortRegsBail %s (general re-sorts finished on the register copy / with more claims "
       "than it holds / abandoned on a failed invariant)" % (st.get("sortsRegs"), st.get("sortRegsOver"), st.get("sortRegsBail")))
+if "stepsOpen" in st:
+    # the main-loop steps by kind, the threshold advances that move, the run capacities that come out 0
+    for kind in ("Open", "Run", "Single"):
+        c, k = st["cycStep" + kind], st["steps" + kind]
+        print("steps %-6s %5d  %5.1f%%  %8.0f cyc/step" % (kind.lower(), k, 100.0 * c / tot, c / max(k, 1)))
+    print("claim_full calls that move a threshold %d of %d (the scan's and one per run): %.1f%% (%.0f cyc each, inside cycFullThr)" % (
+        st["thrMoves"], st["claimFull"] + st["runs"], 100.0 * st["cycThrMove"] / tot, st["cycThrMove"] / max(st["thrMoves"], 1)))
+    calls = st["runCapFront"] + st["runCapFull"]
+    print("claim_run_cap calls %d, returning 0: %d;  capBoundSkips %d;  thrBatchCalls %d thrMultiChunk %d" % (
+        calls, st["runCapZero"], st["capBoundSkips"], st["thrBatchCalls"], st["thrMultiChunk"]))
+    print("chainPods %d of %d main-loop steps" % (st["chainPods"], st["pops"] - st["runPods"]))
 if closed:
     print("cycles per closed re-sort %.0f;  closedShiftDiff %s (moved entries whose shifted value differs from a regather)" % (
         st["cycSortClosed"] / closed, st.get("closedShiftDiff", "n/a")))
