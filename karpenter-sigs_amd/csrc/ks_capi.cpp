@@ -193,6 +193,10 @@ struct ks_results {
   std::vector<ks::Route> routes;  // the k_solve launches of this Solve, in order (a re-plan adds one)
   ks::Plan plan{};                // the LDS plan of the last launch, and its make_plan level (wideKO)
   int planWide = 0;
+  // the handle's fresh-NodeClaim table (KS_TPL_TABLE): built, its request classes, k_fresh_claims' time when it was built
+  bool tplTable = false;
+  int tplClasses = 0;
+  float tplTableMs = 0;
   // First-use rendering writes the claims' caches: serialised, so two threads reading one Results (ctypes
   // and cgo release the interpreter / scheduler around the call) render once; what a call hands out is
   // never rebuilt afterwards.
@@ -288,7 +292,7 @@ static bool node_rows_on(const KsDims& d, size_t FNR) {
   return FNR > 0 && d.N > 0 && fnBytes <= ((size_t)1 << 29) && !getenv("KS_NO_NODE_ROWS");
 }
 
-void ks_upload(ks_problem* pb) {
+void ks_upload(ks_problem* pb, bool classes) {
   Host& h = pb->host;
   auto& t = h.tab;
   Arena a;
@@ -330,6 +334,35 @@ void ks_upload(ks_problem* pb) {
   if (frontPos.empty()) frontPos.push_back(0);
   size_t o_fb = put(frontBeg.data(), frontBeg.size() * 4);
   size_t o_fp = put(frontPos.data(), frontPos.size() * 4);
+  // The LEAN Solve's fresh-NodeClaim block (ks_problem.h tpl_block_*), right behind the fronts, for every lean
+  // problem: the request classes now, the table zeroed until the handle's first Solve fills it (build_tpl_table).
+  // Classes and a table only for a Solve handle, and only while classes x templates x record bytes stays within
+  // kTplTableMaxBytes (KS_TPL_TABLE_MAX_BYTES in the environment overrides the cap, for tests); otherwise every pod's
+  // class is -1 and the Solve derives every NewNodeClaim.
+  std::vector<int32_t> podClass;
+  std::vector<int64_t> classReq;
+  pb->tplClasses = 0;
+  pb->tplBlock = 0;
+  if (h.dims.lean && h.dims.P > 0 && h.dims.NTPL > 0) {
+    const int nw = tpl_memo_words(h.dims.R, h.dims.TW);
+    int ncls = 0;
+    if (classes) {
+      request_classes(h.dims, t.pod_req, podClass, classReq);
+      ncls = pb->tplClasses = (int)(classReq.size() / (size_t)h.dims.R);
+      size_t cap = kTplTableMaxBytes;
+      if (const char* e = getenv("KS_TPL_TABLE_MAX_BYTES")) cap = (size_t)strtoull(e, nullptr, 10);
+      if (4 * (size_t)ncls * (size_t)h.dims.NTPL * (size_t)nw > cap) ncls = 0;
+    }
+    if (ncls == 0) {
+      podClass.assign((size_t)h.dims.P, -1);
+      classReq.clear();
+    }
+    const size_t o_blk = a.add(4 * tpl_block_words(h.dims.P, ncls, h.dims.NTPL, nw, h.dims.R));
+    if (o_blk != o_fp + 4 * tpl_block_base(frontTotal)) throw KsError(KS_ERR_INTERNAL, "fresh-NodeClaim block is not behind the fronts");
+    items.push_back({o_blk, podClass.data(), podClass.size() * 4});
+    items.push_back({o_blk + 4 * tpl_block_req(h.dims.P, ncls, h.dims.NTPL, nw), classReq.data(), classReq.size() * 8});
+    if (ncls) pb->tplBlock = o_blk;
+  }
   size_t o_tsp = put(t.tsort_pos.data(), t.tsort_pos.size() * 4);
   size_t o_pr = put(t.pool_rem0.data(), t.pool_rem0.size() * 8);
   size_t o_pm = put(t.pool_mask.data(), t.pool_mask.size() * 4);
@@ -769,6 +802,10 @@ static ks_results* collect(ks_problem* pb, const KsWork& W) {
   dl(ctr, W.counters, CT_NCOUNTERS, st);
   HIPCHK(hipStreamSynchronize(st));
   if (ctr[CT_ERROR] == KE_CLAIM_CAP) throw claim_cap_error(pb);
+  if (ctr[CT_ERROR] == KE_TPL_TABLE)  // the self-check build (KS_TPL_TABLE_CHECK): the first differing word
+    throw KsError(KS_ERR_INTERNAL, "fresh-NodeClaim record differs from the derivation: word " + std::to_string(ctr[CT_TPL_MASK_FILLS]) +
+                                       ", derived " + std::to_string((uint64_t)ctr[CT_TPL_MASK_HITS] >> 32) + ", record " +
+                                       std::to_string((uint64_t)ctr[CT_TPL_MASK_HITS] & 0xffffffffull));
   if (ctr[CT_ERROR] != KE_OK) throw KsError(KS_ERR_INTERNAL, "solve kernel iteration cap hit");
   int nc = (int)ctr[CT_NCLAIMS], nl = (int)ctr[CT_NLOG];
   std::vector<int32_t> order, ctpl, chost, logp, logt, status, fstate;
@@ -1019,7 +1056,7 @@ static void problem_device_init(ks_problem* pb) {
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0) throw KsError(KS_ERR_HIP, "no HIP device visible");
   HIPCHK(hipGetDevice(&pb->device));
   HIPCHK(hipStreamCreateWithFlags(&pb->stream, hipStreamNonBlocking));
-  ks_upload(pb);
+  ks_upload(pb, true);
   size_t np = std::max(pb->host.dims.P, 1);
   HIPCHK(hipMalloc(&pb->skeys, 2 * np * sizeof(uint64_t)));
   HIPCHK(hipMalloc(&pb->svals, 2 * np * sizeof(int32_t)));
@@ -1211,7 +1248,8 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
        ",\"logRuns\":" + std::to_string(log_runs_build()) + ",\"sortRegs\":" + std::to_string(sort_regs_build()) +
        ",\"sortRegsN64\":" + std::to_string(sort_regs_n64_build()) + ",\"queuePacked\":" + std::to_string(queue_packed_build()) +
        ",\"capBound\":" + std::to_string(cap_bound_build()) + ",\"thrBatch\":" + std::to_string(thr_batch_build()) +
-       ",\"runChain\":" + std::to_string(run_chain_build()) + ",\"paretoFronts\":[";
+       ",\"runChain\":" + std::to_string(run_chain_build()) + ",\"tplTableBuild\":" + std::to_string(tpl_table_build()) +
+       ",\"tplTableCheck\":" + std::to_string(tpl_table_check_build()) + ",\"paretoFronts\":[";
   for (int t = 0; t < d.NTPL; t++) {
     o += t ? ",[" : "[";
     for (int i = frontBeg[(size_t)t]; i < frontBeg[(size_t)t + 1]; i++)
@@ -1240,6 +1278,19 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
   for (size_t i = 0; i < sizeof(budgets) / sizeof(budgets[0]); i++)
     o += (i ? ",\"" : "\"") + std::to_string(budgets[i]) + "\":[" + plan_json(budgets[i], 1) + "," + plan_json(budgets[i], 2) + "]";
   o += "}";
+  {  // the LEAN Solve's fresh-NodeClaim table as build_tpl_table decides it at the default budget (cap: kTplTableMaxBytes)
+    std::vector<int32_t> podClass;
+    std::vector<int64_t> classReq;
+    if (d.lean && d.P > 0) request_classes(d, h.tab.pod_req, podClass, classReq);
+    const long long ncls = (long long)(classReq.size() / (size_t)std::max(d.R, 1));
+    const size_t bytes = 4 * (size_t)ncls * (size_t)d.NTPL * (size_t)tpl_memo_words(d.R, d.TW);
+    bool keys = false;  // (fmOn, as ks_upload sets it, needs a state with label requirements: a lean problem has none)
+    for (int32_t f : h.tab.st_flags) keys = keys || (f & SF_HAS_KEYS);
+    const Plan pl = make_plan(pd, budgets[0], false, 0, (int)frontPos.size());
+    const bool on = tpl_table_build() && ncls > 0 && !keys && !d.G && pl.talloc && (d.R == 3 || d.R == 4) && d.NTPL > 0 &&
+                    bytes <= kTplTableMaxBytes;
+    kv("tplClasses", ncls); kv("tplTableBytes", (long long)bytes); kv("tplTable", on ? 1 : 0);
+  }
   o += ",\"keyNames\":[";
   for (size_t i = 0; i < h.keyNames.size(); i++) { if (i) o += ","; ksjson::quote(o, h.keyNames[i]); }
   o += "],\"resources\":[";
@@ -1481,6 +1532,29 @@ void ks_problem_free(ks_problem* p) {
 }
 void ks_results_free(ks_results* r) { delete r; }
 
+// The LEAN Solve's fresh-NodeClaim table, once per handle, where its first launch plan is known: one k_fresh_claims
+// wave per (request class, template) on the handle's stream, ahead of the Solve.  None when the build has no consumer,
+// the problem will not take the LEAN Solve (not lean, feasibility rows on, a resource count other than 3 or 4, tables
+// not LDS-resident), or the upload made no block (ks_upload: past the cap); the Solve then derives every NewNodeClaim
+// itself.
+static void build_tpl_table(ks_problem* pb, const Plan& pl) {
+  if (pb->tplTableState != 0) return;
+  pb->tplTableState = -1;
+  const KsDims& d = pb->dev.d;
+  if (!tpl_table_build() || pb->tplBlock == 0 || !d.lean || d.fmOn || d.G || !pl.talloc || (d.R != 3 && d.R != 4)) return;
+  hipEvent_t a, b;
+  HIPCHK(hipEventCreate(&a));
+  HIPCHK(hipEventCreate(&b));
+  HIPCHK(hipEventRecord(a, pb->stream));
+  HIPCHK(launch_fresh_claims(pb->dev, pb->works_dev, pl, (uint32_t*)((char*)pb->dbuf + pb->tplBlock), pb->tplClasses, pb->stream));
+  HIPCHK(hipEventRecord(b, pb->stream));
+  HIPCHK(hipEventSynchronize(b));
+  HIPCHK(hipEventElapsedTime(&pb->tplTableMs, a, b));
+  (void)hipEventDestroy(a);
+  (void)hipEventDestroy(b);
+  pb->tplTableState = 1;
+}
+
 int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   API_TRY
   if (!pb || !out) throw KsError(KS_ERR_ARG, "null argument");
@@ -1512,6 +1586,7 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
     pb->wreps = reps;
   }
   KsWork w0 = work_ptrs((char*)pb->wbuf, wl);
+  build_tpl_table(pb, pl);
   hipEvent_t e0, em, ep, e1, ef[4];
   HIPCHK(hipEventCreate(&e0));
   HIPCHK(hipEventCreate(&em));
@@ -1598,6 +1673,9 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   r->routes = routes;
   r->plan = pl;
   r->planWide = wide;
+  r->tplTable = pb->tplTableState == 1;
+  r->tplClasses = pb->tplClasses;
+  r->tplTableMs = pb->tplTableMs;
   r->kernel_ms = ms;
   r->solve_ms = ms - setup - post;
   r->feas_ms = fms;
@@ -1649,9 +1727,11 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "cycTplCand", "cycTplFeas", "cycTplFilter", "cycTplThr", "cycLogLoad", "cycLogStore",
                                 "capBoundSkips", "thrBatchCalls", "thrMultiChunk", "chainPods",
                                 "cycStepOpen", "cycStepRun", "cycStepSingle", "stepsOpen", "stepsRun", "stepsSingle",
-                                "thrMoves", "cycThrMove", "runCapZero"};
+                                "thrMoves", "cycThrMove", "runCapZero", "tplTableHits"};
   static_assert(sizeof(names) / sizeof(names[0]) == CT_NCOUNTERS, "one name per counter");
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);
+  o += ",\"tplTable\":" + std::to_string(r->tplTable ? 1 : 0) + ",\"tplClasses\":" + std::to_string(r->tplClasses) +
+       ",\"tplTableMs\":" + std::to_string(r->tplTableMs);
   // the launched k_solve instantiation: the last launch's fields, and every launch of this Solve in order
   if (!r->routes.empty()) {
     std::string last = routes_json({r->routes.back()});

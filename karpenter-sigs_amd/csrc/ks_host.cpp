@@ -1639,4 +1639,22 @@ void pareto_fronts(const KsDims& dims, const std::vector<int32_t>& tpl_it_beg, c
   }
 }
 
+void request_classes(const KsDims& dims, const std::vector<int64_t>& pod_req, std::vector<int32_t>& cls,
+                     std::vector<int64_t>& req) {
+  const size_t R = (size_t)dims.R, P = (size_t)dims.P;
+  cls.assign(P, 0);
+  req.clear();
+  std::map<std::vector<int64_t>, int32_t> ids;
+  std::vector<int64_t> key(R);
+  for (size_t p = 0; p < P; p++) {
+    key.assign(pod_req.begin() + (ptrdiff_t)(p * R), pod_req.begin() + (ptrdiff_t)((p + 1) * R));
+    auto it = ids.find(key);
+    if (it == ids.end()) {
+      it = ids.emplace(key, (int32_t)ids.size()).first;
+      req.insert(req.end(), key.begin(), key.end());
+    }
+    cls[p] = it->second;
+  }
+}
+
 }  // namespace ks

@@ -277,6 +277,12 @@ constexpr int kFrontMax = 64;
 void pareto_fronts(const KsDims& dims, const std::vector<int32_t>& tpl_it_beg, const std::vector<int32_t>& tpl_its,
                    const std::vector<int64_t>& it_alloc, std::vector<int32_t>& beg, std::vector<int32_t>& pos);
 
+// Request classes of a LEAN problem (KsDims::lean): the pods' request vectors over all R resources, deduplicated in
+// order of first appearance.  cls[p]: the class of pod p; req: [classes][R].  Derived at upload from the requests (the
+// JSON and the binary snapshot routes alike), never stored.  The LEAN Solve's fresh-NodeClaim table is indexed by them.
+void request_classes(const KsDims& dims, const std::vector<int64_t>& pod_req, std::vector<int32_t>& cls,
+                     std::vector<int64_t>& req);
+
 // The topology tables' shape for the inspectors (ks_topo.cpp), as JSON members without braces: tgSmall, tgCntWords,
 // TK, topologyKeys (key names in key-slot order) and topologyGroups ([slot, nv, small, type, host] per group).
 std::string topo_inspect_json(const Host& h);

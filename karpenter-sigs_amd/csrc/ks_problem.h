@@ -6,6 +6,7 @@
 // (ks_reqset.h), taint bitmasks and CSR instance-type lists.  The tables are written once by
 // ks_problem_create and stay resident; each ks_solve gets a fresh workspace.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "ks_reqset.h"
@@ -211,7 +212,37 @@ struct KsDev {
   const int32_t KS_G* tpl_front_beg;  // [NTPL+1]
   const int32_t KS_G* tpl_front;      // [frontTotal] template positions, ascending
   int32_t frontTotal;
+  // LEAN problems (KS_TPL_TABLE): behind tpl_front, at tpl_front + tpl_block_base(frontTotal), lies the fresh-NodeClaim
+  // block (below).  It has no field here: this struct is a kernel argument of every k_solve instantiation, and its
+  // layout stays what it was.
 };
+
+// The fresh-NodeClaim block of a LEAN problem (ks_capi.cpp ks_upload, k_fresh_claims), in 32-bit words.  Its base
+// follows the front positions in the problem's allocation (whose arrays are 256-byte aligned, at least 16 bytes long).
+// From the base: pod_class [P] (int32): the pod's request class (ks_host.cpp request_classes), -1: no table (a
+// consolidation handle; classes x templates x record bytes past kTplTableMaxBytes); the table
+// [classes][NTPL][tpl_memo_words] (uint32): per (class, template) the record k_fresh_claims writes once per handle, in
+// the layout of the LEAN Solve's NewNodeClaim memo, zero until then (a record without options: the Solve derives);
+// class_req [classes][R] (int64, 8-byte aligned: the base is).
+KS_HD constexpr size_t tpl_block_base(int frontTotal) {
+  return ((4 * (size_t)(frontTotal > 4 ? frontTotal : 4) + 255) & ~(size_t)255) / 4;
+}
+KS_HD constexpr size_t tpl_block_table(int P) { return ((size_t)P + 63) & ~(size_t)63; }
+KS_HD constexpr size_t tpl_block_req(int P, int ncls, int NTPL, int nw) {
+  return tpl_block_table(P) + (((size_t)ncls * (size_t)NTPL * (size_t)nw + 1) & ~(size_t)1);
+}
+KS_HD constexpr size_t tpl_block_words(int P, int ncls, int NTPL, int nw, int R) {
+  return tpl_block_req(P, ncls, NTPL, nw) + 2 * (size_t)ncls * (size_t)R;
+}
+
+// LDS / table words of one NewNodeClaim memo record (ks_solve.hip Solver::s_memo, k_fresh_claims): [4] template,
+// option count, front flag, pad; [R] pod requests, [R] max Allocatable (int64); [R] thresholds; [TW] options; R spare
+// words (the size make_plan has always reserved)
+KS_HD constexpr int tpl_memo_words(int R, int TW) { return TW + 6 * R + 4; }
+// k_fresh_claims' table is built only while classes x templates x record bytes stays within this (KS_TPL_TABLE_MAX_BYTES
+// overrides it for tests): a Solve of P pods opens at most P NodeClaims, and a table larger than a few MiB costs more to
+// fill than the derivations it replaces
+constexpr size_t kTplTableMaxBytes = (size_t)4 << 20;
 
 enum NodeFlag : int32_t { NF_UNUSABLE = 1 };
 enum TopoGroupType : int32_t { TG_SPREAD = 0, TG_AFFINITY = 1, TG_ANTI = 2 };
@@ -375,7 +406,8 @@ enum Counter {
   // the cycles of their advance (inside cycFullThr); claim_run_cap calls that returned 0
   CT_KIND,
   CT_KIND_END = CT_KIND + 9,
-  CT_NCOUNTERS = CT_KIND_END
+  CT_TPL_TABLE_HITS = CT_KIND_END,  // LEAN Solve NewNodeClaims that missed the memo and took k_fresh_claims' record (KS_TPL_TABLE)
+  CT_NCOUNTERS
 };
 enum SplitSub { YS_TPL_CAND = 0, YS_TPL_FEAS, YS_TPL_FILTER, YS_TPL_THR, YS_LOG_LOAD, YS_LOG_STORE };
 enum KindSub { KD_CYC_OPEN = 0, KD_CYC_RUN, KD_CYC_SINGLE, KD_N_OPEN, KD_N_RUN, KD_N_SINGLE, KD_THR_MOVES, KD_CYC_THR_MOVE, KD_CAP_ZERO };
@@ -395,6 +427,7 @@ enum StepSub {
   SS_TPL_MAX,        // try_templates: recompute_max
 };
 // KE_LEAN_EXIT: a LEAN Solve of pods sharing a UID met its first push-back (the host re-runs it non-LEAN)
-enum KernelError { KE_OK = 0, KE_CLAIM_CAP = 1, KE_ITER_CAP = 2, KE_STACK = 3, KE_LEAN_EXIT = 4 };
+// KE_TPL_TABLE: the self-check build (-DKS_TPL_TABLE_CHECK=1) derived other words than k_fresh_claims' record holds
+enum KernelError { KE_OK = 0, KE_CLAIM_CAP = 1, KE_ITER_CAP = 2, KE_STACK = 3, KE_LEAN_EXIT = 4, KE_TPL_TABLE = 5 };
 
 }  // namespace ks

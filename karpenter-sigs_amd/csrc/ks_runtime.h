@@ -38,6 +38,10 @@ int queue_packed_build();  // KS_QUEUE_PACKED ("queuePacked", ks_queue.hip)
 int cap_bound_build();     // KS_CAP_BOUND ("capBound"), KS_THR_BATCH ("thrBatch")
 int thr_batch_build();
 int run_chain_build();     // KS_RUN_CHAIN ("runChain")
+int tpl_table_build();     // KS_TPL_TABLE ("tplTableBuild") and its self-check, KS_TPL_TABLE_CHECK ("tplTableCheck")
+int tpl_table_check_build();
+// k_fresh_claims (ks_solve.hip): ncls x NTPL records into the fresh-NodeClaim block at blk (device), R 3 or 4
+hipError_t launch_fresh_claims(const KsDev& D, const KsWork* works, const Plan& pl, uint32_t* blk, int ncls, hipStream_t st);
 // ks_claim_sort_probe's kernel (ks_solve.hip): device pointers, how [64] (how, path); n <= kProbeMaxN, R 3 or 4
 hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,
                             const int64_t* chead, int32_t* ptpl, int64_t* phead, int32_t* how, hipStream_t st);
@@ -118,6 +122,11 @@ struct ks_problem {
   void* stemp = nullptr;
   size_t stempBytes = 0;
   int32_t* hqorder = nullptr;  // [P] NewQueue order from the host (Host::hostQueue), when pods tie
+  // The LEAN Solve's fresh-NodeClaim table (KS_TPL_TABLE): built by the handle's first Solve, kept until the handle goes
+  int tplClasses = 0;          // request classes of a LEAN Solve handle (0: none)
+  size_t tplBlock = 0;         // byte offset of the fresh-NodeClaim block in dbuf when it holds classes and a table
+  int tplTableState = 0;       // 0 not decided yet, 1 built, -1 none (see build_tpl_table)
+  float tplTableMs = 0;        // k_fresh_claims by events, when it was built
   ~ks_problem() {
     int prev = -1;
     if (device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device) (void)hipSetDevice(device);
@@ -158,7 +167,8 @@ struct DeviceGuard {
 }  // namespace ks
 
 // Upload the host tables to one HBM allocation and point pb->dev at them.
-void ks_upload(ks_problem* pb);
+// classes: also the request classes of a LEAN problem (a Solve handle; a consolidation handle has none)
+void ks_upload(ks_problem* pb, bool classes = false);
 
 // Binary snapshots (ks_capi.cpp): a magic, the format version and the sizes of the shared structs.
 namespace ks { struct ArOut; struct ArIn; }

@@ -100,6 +100,17 @@
 #ifndef KS_TPL_MASKS
 #define KS_TPL_MASKS 0
 #endif
+// LEAN Solve: 1 lets a NewNodeClaim that misses the memo take the record k_fresh_claims wrote for (the pod's request
+// class, the template) once per handle, instead of deriving it on the one-wave chain (0: derives it, as before).
+// Compiled out with KS_TPL_MASKS=1, whose variant build measures the masks' path alone.
+#ifndef KS_TPL_TABLE
+#define KS_TPL_TABLE 1
+#endif
+// Self-check build: a NewNodeClaim that would take a record derives it as well and compares every word; a mismatch
+// ends the Solve with KE_TPL_TABLE
+#ifndef KS_TPL_TABLE_CHECK
+#define KS_TPL_TABLE_CHECK 0
+#endif
 // LEAN Solve: a run past the queue window, while the queue is still NewQueue's order, logs one record and
 // k_log_expand writes its per-pod entries after the Solve (0: the wave reads the pods back, 64 per load)
 #ifndef KS_LOG_RUNS
@@ -636,8 +647,6 @@ __global__ __launch_bounds__(256) void k_feasibility_nodes(KsDev D, int nbx) {
 // A topology simulation keeps its register window's node domains in LDS (Solver::s_tdw): the first kTdw nodes,
 // the first kTdwKeys key slots (make_plan counts the bytes).
 constexpr int kTdw = 256, kTdwKeys = 4;
-// LDS words of the LEAN Solve's NewNodeClaim memo (Solver::s_memo; make_plan counts the bytes)
-constexpr int tpl_memo_words(int R, int TW) { return TW + 6 * R + 4; }
 
 // The claim order and its re-sort: s.newNodeClaims as claim ids and pod counts per sorted position, and the
 // wave-parallel replay of Go's pdqsort_func over them.  Kept apart from Solver (which derives from it) so that the
@@ -1228,6 +1237,14 @@ struct Solver : ClaimSort {
   LU32 s_tmask;         // [NTPL][2 * TW]
   LU32 s_tmv;           // [NTPL]
   int64_t maskFills = 0, maskHits = 0;
+  // LEAN Solve (KS_TPL_TABLE, when the handle holds the table: ks_problem.h): a NewNodeClaim that misses the memo under
+  // the memo's conditions copies k_fresh_claims' record of (the pod's request class, t) into s_memo and goes on as a hit
+  static constexpr bool TPL_TABLE = KS_TPL_TABLE && !KS_TPL_MASKS && TPL_MEMO;
+  static constexpr bool TPL_TABLE_CHECK = KS_TPL_TABLE_CHECK && TPL_TABLE;
+  // (its counter is a member of the LEAN Solve alone: the other instantiations' Solver keeps its layout)
+  struct TableHits { int64_t n = 0; };
+  struct NoTableHits {};
+  [[no_unique_address]] std::conditional_t<TPL_TABLE, TableHits, NoTableHits> tableHits;
   // LEAN Solve (KS_RUN_FRONT): the templates' Pareto fronts (KsDev::tpl_front), and per LDS-resident claim whether
   // its options held every front member that fitted its first requests (try_templates): bit TPL_FOK of lc.tpl
   static constexpr bool RUN_FRONT = KS_RUN_FRONT && KS_CLAIM_RUNS && LEAN && !SIM;
@@ -2620,7 +2637,8 @@ struct Solver : ClaimSort {
   }
 
   // --- new NodeClaim from each template in order (scheduler.go:258-283) -----------------------
-  // Returns 1 placed, 0 failed (fail codes recorded), 2 no templates (add() returns nil), -1 cap.
+  // Returns 1 placed, 0 failed (fail codes recorded), 2 no templates (add() returns nil), -1 cap, -2 a record of
+  // k_fresh_claims differs from the derivation (KS_TPL_TABLE_CHECK).
   __device__ __forceinline__ int try_templates(int p, int s, int sflags, uint64_t toltpl, const int64_t* pod,
                                                int& nclaims, int& nlog, int& hostCtr, bool& srt) {
     if (d.NTPL == 0) return 2;
@@ -2660,9 +2678,17 @@ struct Solver : ClaimSort {
         }
       }
       const LU32 tm_ic = TPL_MASKS ? s_tmask + (int64_t)t * 2 * d.TW : s_tmask, tm_of = TPL_MASKS ? tm_ic + d.TW : s_tmask;
+      // KS_TPL_TABLE: under the memo's conditions everything the memo keeps is a function of (t, the pod's requests),
+      // and the handle holds it for every (request class, template): k_fresh_claims ran this derivation once, one
+      // wave per pair.  A miss loads the pod's class and the record; a record with options becomes the memo's content
+      // and the claim is created as on a hit (the memo then holds what the derivation would have left in it, so its
+      // later hits are the same ones).  A record without options takes the derivation, which sets the failure flags.
+      bool tabTry = false, tab = false;
+      const uint32_t KS_G* chk = nullptr;  // KS_TPL_TABLE_CHECK: the record to compare the derivation with
+      if constexpr (TPL_TABLE) tabTry = pool < 0 && !d.fmOn && !hit;
       // filterByRemainingResources (scheduler.go:364-383)
       uint64_t anyCand = 0;
-      for (int base = 0; base < (hit || mk ? 0 : nIT); base += kWave) {
+      for (int base = 0; base < (hit || mk || tabTry ? 0 : nIT); base += kWave) {  // (tabTry: no limit, all candidates)
         const int pos = base + lane();
         bool ok = pos < nIT;
         if (ok && pool >= 0) {
@@ -2718,6 +2744,27 @@ struct Solver : ClaimSort {
             for (int r = 0; r < R(); r++) req[r] = D.tpl_daemon[(int64_t)t * R() + r] + pod[r];
             uint32_t flags = 0;
             uint64_t any = 0;
+            if constexpr (TPL_TABLE) {
+              if (tabTry) {
+                const int nw = tpl_memo_words(R(), d.TW);
+                // the block: pod_class, then the table (ks_problem.h).  Class -1: this handle has no table
+                const int32_t KS_G* blk = D.tpl_front + tpl_block_base(D.frontTotal);
+                const int cls = uni(blk[p]);
+                const uint32_t KS_G* rec = (const uint32_t KS_G*)blk + tpl_block_table(d.P) + ((int64_t)(cls < 0 ? 0 : cls) * d.NTPL + t) * nw;
+                const uint32_t v0 = cls >= 0 && lane() < nw ? rec[lane()] : 0u;  // one lane per word
+                if (rdl((int)v0, MM_CNT) > 0) {
+                  tableHits.n++;
+                  if constexpr (TPL_TABLE_CHECK) {
+                    chk = rec;
+                  } else {
+                    if (lane() < nw) s_memo[lane()] = v0;
+                    for (int i = kWave + lane(); i < nw; i += kWave) s_memo[i] = rec[i];
+                    wsync();
+                    hit = tab = true;
+                  }
+                }
+              }
+            }
             if (hit) {  // the memo's options
               copy_words(s_rem, s_memo + MM_POD + 5 * R(), d.TW);
               any = 1;
@@ -2729,7 +2776,7 @@ struct Solver : ClaimSort {
             PH_BEGIN(tyl);
             for (int base = 0; base < (hit ? 0 : nIT); base += kWave) {
               const int pos = base + lane();
-              const bool in = pos < nIT && (mk || ((s_cand[pos >> 5] >> (pos & 31)) & 1u));
+              const bool in = pos < nIT && (mk || tabTry || ((s_cand[pos >> 5] >> (pos & 31)) & 1u));
               bool ic = false, fi = false, of = false;
               if (in) {
                 if (mk) {
@@ -2858,7 +2905,7 @@ struct Solver : ClaimSort {
                 }
                 if (!inl) hbm_release();
                 wsync();
-                memoHits++;
+                if (!tab) memoHits++;
               } else {
                 if (mk) maskHits++;
                 if (inl) recompute_max<true>(c, s_rem, t, c);
@@ -2876,6 +2923,27 @@ struct Solver : ClaimSort {
                     s_memo[MM_CNT] = (uint32_t)cnt;
                     if constexpr (RUN_FRONT) s_memo[MM_FOK] = fok ? 1u : 0u;
                     wsync();
+                    if constexpr (TPL_TABLE_CHECK) {
+                      if (chk) {  // every word the derivation left in the memo against the record's (word 3 and the R
+                                  // words behind the options are padding)
+                        // (the first differing word goes to the host in the masks' counters, which the table's
+                        // build leaves unused: KS_TPL_MASKS is off with it)
+                        int bi = -1;
+                        uint32_t bd = 0, br = 0;
+                        for (int i = lane(); i < MM_POD + 5 * R() + d.TW; i += kWave)
+                          if (bi < 0 && i != 3 && s_memo[i] != chk[i]) {
+                            bi = i;
+                            bd = s_memo[i];
+                            br = chk[i];
+                          }
+                        if (const uint64_t bm = wballot(bi >= 0)) {
+                          const int l = ctz64(bm);
+                          maskFills = rdl(bi, l);
+                          maskHits = (int64_t)(((uint64_t)(uint32_t)rdl((int)bd, l) << 32) | (uint32_t)rdl((int)br, l));
+                          return -2;
+                        }
+                      }
+                    }
                   }
                 }
               }
@@ -2904,6 +2972,60 @@ struct Solver : ClaimSort {
       W.fail_host[(int64_t)p * d.NTPL + t] = hostid;
     }
     return 0;
+  }
+
+  // k_fresh_claims: what try_templates' derivation leaves in s_memo for a fresh NodeClaim of template t (no NodePool
+  // limit, no feasibility rows) and a pod with these requests -- every position a candidate, the template's own
+  // requirement record in s_rs, the same feas_masks / irregular-position tests, Fits of tpl_daemon[t] + pod, the
+  // threshold counts, the front test and recompute_max, written through lc.max.  No option left: count 0 and the key.
+  __device__ __forceinline__ void fresh_record(int t, const int64_t* pod) {
+    const int tb = s_tbeg[t], nIT = s_tbeg[t + 1] - tb;
+    int64_t req[RM];
+    for (int r = 0; r < R(); r++) req[r] = D.tpl_daemon[(int64_t)t * R() + r] + pod[r];
+    for (int i = lane(); i < tpl_memo_words(R(), d.TW); i += kWave) s_memo[i] = 0;
+    for (int i = lane(); i < d.TW; i += kWave) s_rem[i] = 0;
+    copy_words(s_rs, D.tpl_rs + (int64_t)t * d.RSW, d.RSW);
+    wsync();
+    feas_masks(s_rs, t);
+    for (int base = 0; base < nIT; base += kWave) {
+      const int pos = base + lane();
+      bool ic = false, fi = false, of = false;
+      if (pos < nIT) {
+        if (fbit(s_firr, pos)) {
+          const int it = D.tpl_its[tb + pos];
+          ic = rs_intersects(L, D.it_rs + (int64_t)it * d.RSW, s_rs);
+          of = has_offering(it, s_rs);
+        } else {
+          ic = fbit(s_fic, pos);
+          of = fbit(s_fof, pos);
+        }
+        fi = fits_pos(req, tb + pos);
+      }
+      store_bits(s_rem, base, wballot(ic && fi && of));
+    }
+    wsync();
+    const int cnt = popc_words(s_rem, d.TW);
+    const LI64 mp = (LI64)(s_memo + MM_POD);
+    for (int r = 0; r < R(); r++) mp[r] = pod[r];  // wave-wide stores of uniform values (see commit_claim)
+    s_memo[MM_T] = (uint32_t)t;
+    s_memo[MM_CNT] = (uint32_t)cnt;
+    if (cnt > 0) {
+      for (int r = 0; r < R(); r++) {
+        const int64_t b = (int64_t)tb * R() + (int64_t)r * nIT;
+        int k = 0;
+        for (int q = 0; q < nIT; q += kWave)
+          k += __popcll(wballot(q + lane() < nIT && tsort_a(b + q + lane()) < req[r]));
+        s_memo[MM_POD + 4 * R() + r] = (uint32_t)k;
+      }
+      const int fb = s_fbeg[t], nf = s_fbeg[t + 1] - fb;
+      const int q = lane() < nf ? s_front[fb + lane()] : 0;
+      const bool miss = lane() < nf && fits_pos(req, tb + q) && !((s_rem[q >> 5] >> (q & 31)) & 1u);
+      s_memo[MM_FOK] = nf > 0 && wballot(miss) == 0 ? 1u : 0u;
+      copy_words(s_memo + MM_POD + 5 * R(), s_rem, d.TW);
+      lc.max = mp + R();  // claim 0's max Allocatable is the record's
+      recompute_max<true>(0, s_rem, t, -1);
+    }
+    wsync();
   }
 
   // try_templates' NewNodeClaim calls for a pod every template fails on topology (simNoClaim): a template whose
@@ -3723,6 +3845,75 @@ hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int 
   const size_t lds = 8 * (size_t)n * R + 3 * ((4 * (size_t)n + 15) & ~(size_t)15) + 16;
   if (R == 3) hipLaunchKernelGGL((k_claim_sort_probe<3>), dim3(1), dim3(kWave), lds, st, keys, order, n, mode, pos, ctpl, chead, ptpl, phead, how);
   else hipLaunchKernelGGL((k_claim_sort_probe<4>), dim3(1), dim3(kWave), lds, st, keys, order, n, mode, pos, ctpl, chead, ptpl, phead, how);
+  return hipGetLastError();
+}
+
+// The LEAN Solve's fresh-NodeClaim table (KS_TPL_TABLE): one wave per (request class, template) runs the derivation
+// try_templates would run on the Solve's one-wave chain (Solver::fresh_record) and writes its memo record to
+// table[(class * NTPL + t) * tpl_memo_words]; blk is the block's base (ks_problem.h tpl_block_*), the class count the
+// grid's.  Templates with a NodePool limit are never looked up (the memo's conditions); their records stay as the
+// upload zeroed them.  The instance-type tables are read from HBM (TL false):
+// a wave needs the key metadata, the template offsets and fronts and the scratch bitsets in LDS, nothing else.
+template <int RT>
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_fresh_claims(KsDev D, const KsWork* works, Plan pl,
+                                                                                    uint32_t* blk) {
+  extern __shared__ __attribute__((aligned(16))) char smem_fresh[];
+  const KsDims& d = D.d;
+  const int cls = (int)blockIdx.x / d.NTPL, t = (int)blockIdx.x % d.NTPL;
+  if (D.tpl_pool[t] >= 0) return;
+  Solver<RT, false, false, false, true> S(D, ((const KsWork KS_C*)works)[0], pl);
+  char KS_L* sp = (char KS_L*)smem_fresh;
+  auto take = [&](size_t bytes) { char KS_L* r = sp; sp += (bytes + 15) & ~(size_t)15; return r; };
+  KeyMeta KS_L* s_keys = (KeyMeta KS_L*)take(sizeof(KeyMeta) * d.NK);
+  S.s_tbeg = (LI32)take(4 * (size_t)(d.NTPL + 1));
+  S.s_fbeg = (LI32)take(4 * (size_t)(d.NTPL + 1));
+  S.s_front = (LI32)take(4 * (size_t)D.frontTotal);
+  S.s_rs = (LU32)take(4 * (size_t)d.RSW);
+  S.s_rem = (LU32)take(4 * (size_t)d.TW + 8);
+  S.s_fic = (LU32)take(4 * (size_t)d.TW + 8);
+  S.s_fof = (LU32)take(4 * (size_t)d.TW + 8);
+  S.s_firr = (LU32)take(4 * (size_t)d.TW + 8);
+  S.s_memo = (LU32)take(4 * (size_t)tpl_memo_words(RT, d.TW));
+  for (int i = lane(); i < d.NK * (int)(sizeof(KeyMeta) / 4); i += kWave)
+    ((uint32_t KS_L*)s_keys)[i] = ((const uint32_t KS_G*)D.keys)[i];
+  for (int i = lane(); i <= d.NTPL; i += kWave) {
+    S.s_tbeg[i] = D.tpl_it_beg[i];
+    S.s_fbeg[i] = D.tpl_front_beg[i];
+  }
+  for (int i = lane(); i < D.frontTotal; i += kWave) S.s_front[i] = D.tpl_front[i];
+  S.L.nkeys = d.NK;
+  S.L.W = d.W;
+  S.L.NB = d.NB;
+  S.L.HDR = d.HDR;
+  S.L.RSW = d.RSW;
+  S.L.keys = s_keys;
+  S.L.wordValid = D.wordValid;
+  S.L.vIsInt = D.vIsInt;
+  S.L.vInt = D.vInt;
+  wsync();
+  const int nw = tpl_memo_words(RT, d.TW), ncls = (int)gridDim.x / d.NTPL;
+  const int64_t KS_G* class_req = (const int64_t KS_G*)((const uint32_t KS_G*)blk + tpl_block_req(d.P, ncls, d.NTPL, nw));
+  int64_t pod[RT];
+#pragma unroll
+  for (int r = 0; r < RT; r++) pod[r] = class_req[(int64_t)cls * RT + r];
+  S.fresh_record(t, pod);
+  uint32_t KS_G* out = (uint32_t KS_G*)blk + tpl_block_table(d.P) + (int64_t)blockIdx.x * nw;
+  for (int i = lane(); i < nw; i += kWave) out[i] = S.s_memo[i];
+}
+int tpl_table_build() { return KS_TPL_TABLE && !KS_TPL_MASKS && KS_TPL_MEMO; }
+int tpl_table_check_build() { return tpl_table_build() && KS_TPL_TABLE_CHECK; }
+// ncls x NTPL waves; blk: the block's base on the device (pod_class and class_req uploaded, the table zeroed).  R 3 or
+// 4: the LEAN Solve's resource counts (launch_family).
+hipError_t launch_fresh_claims(const KsDev& D, const KsWork* works, const Plan& pl, uint32_t* blk, int ncls, hipStream_t st) {
+  const KsDims& d = D.d;
+  if (ncls <= 0 || d.NTPL <= 0 || (d.R != 3 && d.R != 4)) return hipErrorInvalidValue;
+  auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t lds = r16(sizeof(KeyMeta) * d.NK) + 2 * r16(4 * (size_t)(d.NTPL + 1)) + r16(4 * (size_t)D.frontTotal) +
+                     r16(4 * (size_t)d.RSW) + 4 * r16(4 * (size_t)d.TW + 8) + r16(4 * (size_t)tpl_memo_words(d.R, d.TW));
+  if (lds > 64 * 1024) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(ncls * d.NTPL));
+  if (d.R == 3) hipLaunchKernelGGL((k_fresh_claims<3>), grid, dim3(kWave), lds, st, D, works, pl, blk);
+  else hipLaunchKernelGGL((k_fresh_claims<4>), grid, dim3(kWave), lds, st, D, works, pl, blk);
   return hipGetLastError();
 }
 

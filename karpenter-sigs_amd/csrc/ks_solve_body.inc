@@ -1285,7 +1285,11 @@
       hostCtr = UI(hostCtr);
       srt = U(srt);
       dpos = -1;  // a descent left here is an appended claim's
-      if (r < 0) { err = KE_CLAIM_CAP; break; }
+      if (r < 0) {
+        err = KE_CLAIM_CAP;
+        if constexpr (decltype(S)::TPL_TABLE_CHECK) err = r == -2 ? KE_TPL_TABLE : KE_CLAIM_CAP;
+        break;
+      }
       if (r == 1) placed = true;
       if constexpr (CHAINB) onClaim = r == 1;
 #ifdef KS_PHASE_STATS
@@ -1399,6 +1403,7 @@
     W.counters[CT_TPL_MASK_FILLS] = S.maskFills;
     W.counters[CT_TPL_MASK_HITS] = S.maskHits;
     W.counters[CT_RUN_RECS] = S.runRecs;
+    if constexpr (decltype(S)::TPL_TABLE) W.counters[CT_TPL_TABLE_HITS] = S.tableHits.n;
     if constexpr (decltype(S)::SORT_REGS) {  // (k_init zeroed them: the other instantiations' code stays as it was)
       W.counters[CT_SORT_REGS] = S.sortsRegs;
       W.counters[CT_SORT_REGS_BAIL] = S.sortRegsBail;
