@@ -183,6 +183,13 @@ int ks_claim_sort_probe(int device, int mode, int pos, int n, int R, int32_t* ke
 int ks_claim_sort_probe_path(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
                              const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead,
                              int* how, int* path);
+/* The same for a claim appended behind greater counts -- keys non-decreasing on [0, n - 1), keys[n - 1] below
+ * keys[n - 2] -- with that origin told to the kernel, as the Solve tells it: from 50 entries on the re-sort is then a
+ * closed form (the new entry goes behind the last count not above its own, the entries after it move one place).
+ * *how as above (0 when the closed form ran); *taken (may be NULL): 1 when it ran.  device < 0: Go's pdqsort_func on
+ * the host (*how 1, *taken 0). */
+int ks_claim_sort_probe_append(int device, int n, int R, int32_t* keys, int32_t* order, const int32_t* claim_tpl,
+                               const int64_t* claim_head, int32_t* ptpl, int64_t* phead, int* how, int* taken);
 /* k_rec_headers (the device-side record invariants and header compaction of a consolidation pass) without a
  * handle.  records: the passes' record batches back to back, pass i holding pass_ns[i] records of RF_HDR + 3 * TW
  * int32 words; tpl_beg: ntpl + 1 offsets, template t's instance-type list has tpl_beg[t + 1] - tpl_beg[t] <= 32 * TW

@@ -1249,7 +1249,10 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
        ",\"sortRegsN64\":" + std::to_string(sort_regs_n64_build()) + ",\"queuePacked\":" + std::to_string(queue_packed_build()) +
        ",\"capBound\":" + std::to_string(cap_bound_build()) + ",\"thrBatch\":" + std::to_string(thr_batch_build()) +
        ",\"runChain\":" + std::to_string(run_chain_build()) + ",\"tplTableBuild\":" + std::to_string(tpl_table_build()) +
-       ",\"tplTableCheck\":" + std::to_string(tpl_table_check_build()) + ",\"paretoFronts\":[";
+       ",\"tplTableCheck\":" + std::to_string(tpl_table_check_build()) + ",\"pivotArith\":" + std::to_string(pivot_arith_build()) +
+       ",\"pivotArithCheck\":" + std::to_string(pivot_arith_check_build()) +
+       ",\"appendClosed\":" + std::to_string(append_closed_build()) +
+       ",\"crossQuickFrom\":" + std::to_string(cross_quick_from_build()) + ",\"paretoFronts\":[";
   for (int t = 0; t < d.NTPL; t++) {
     o += t ? ",[" : "[";
     for (int i = frontBeg[(size_t)t]; i < frontBeg[(size_t)t + 1]; i++)
@@ -1464,9 +1467,27 @@ int ks_claim_sort_probe(int device, int mode, int pos, int n, int R, int32_t* ke
 }
 // ... with the general re-sort's path (register copy or LDS code); device -2 / -3: the register copy's lane model
 // on the host (ks_sort_regs.h), 128 / 64 entries
+static int claim_sort_probe_run(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
+                                const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead,
+                                int* how, int* path, int* taken);
 int ks_claim_sort_probe_path(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
                              const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead,
                              int* how, int* path) {
+  return claim_sort_probe_run(device, mode, pos, n, R, keys, order, claim_tpl, claim_head, ptpl, phead, how, path, nullptr);
+}
+// ... as for a claim appended behind greater counts, the origin told to the kernel (sort_claims' `app`, kernel mode 2);
+// *taken: its closed form ran (KS_APPEND_CLOSED).  The host mode is Go's sort all the same
+int ks_claim_sort_probe_append(int device, int n, int R, int32_t* keys, int32_t* order, const int32_t* claim_tpl,
+                               const int64_t* claim_head, int32_t* ptpl, int64_t* phead, int* how, int* taken) {
+  int t = 0;
+  const int rc = claim_sort_probe_run(device, 0, -1, n, R, keys, order, claim_tpl, claim_head, ptpl, phead, how, nullptr, &t);
+  if (taken) *taken = t;
+  return rc;
+}
+// taken != null: the append origin
+static int claim_sort_probe_run(int device, int mode, int pos, int n, int R, int32_t* keys, int32_t* order,
+                                const int32_t* claim_tpl, const int64_t* claim_head, int32_t* ptpl, int64_t* phead,
+                                int* how, int* path, int* taken) {
   API_TRY
   if (const char* bad = sort_probe_check(mode, pos, n, R, keys, order, claim_tpl, claim_head, ptpl, phead))
     throw KsError(KS_ERR_ARG, bad);
@@ -1510,18 +1531,19 @@ int ks_claim_sort_probe_path(int device, int mode, int pos, int n, int R, int32_
     HIPCHK(hipMemcpyAsync(b.ctpl, claim_tpl, 4 * (size_t)n, hipMemcpyHostToDevice, b.stream));
     HIPCHK(hipMemcpyAsync(b.chead, claim_head, 8 * (size_t)n * R, hipMemcpyHostToDevice, b.stream));
   }
-  HIPCHK(claim_sort_probe(b.keys, b.order, n, mode, pos, R, b.ctpl, b.chead, b.ptpl, b.phead, b.how, b.stream));
-  int32_t h[2] = {-1, 0};  // how, path
+  HIPCHK(claim_sort_probe(b.keys, b.order, n, taken ? 2 : mode, pos, R, b.ctpl, b.chead, b.ptpl, b.phead, b.how, b.stream));
+  int32_t h[3] = {-1, 0, 0};  // how, path, the appended claim's closed form ran
   if (n > 0) {
     HIPCHK(hipMemcpyAsync(keys, b.keys, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipMemcpyAsync(order, b.order, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipMemcpyAsync(ptpl, b.ptpl, 4 * (size_t)n, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipMemcpyAsync(phead, b.phead, 8 * (size_t)n * R, hipMemcpyDeviceToHost, b.stream));
   }
-  HIPCHK(hipMemcpyAsync(h, b.how, 8, hipMemcpyDeviceToHost, b.stream));
+  HIPCHK(hipMemcpyAsync(h, b.how, 12, hipMemcpyDeviceToHost, b.stream));
   HIPCHK(hipStreamSynchronize(b.stream));
   if (how) *how = h[0];
   if (path) *path = h[1];
+  if (taken) *taken = h[2];
   return KS_OK;
   API_CATCH
 }
@@ -1727,7 +1749,9 @@ int ks_results_json(const ks_results* r, char** json_out) {
                                 "cycTplCand", "cycTplFeas", "cycTplFilter", "cycTplThr", "cycLogLoad", "cycLogStore",
                                 "capBoundSkips", "thrBatchCalls", "thrMultiChunk", "chainPods",
                                 "cycStepOpen", "cycStepRun", "cycStepSingle", "stepsOpen", "stepsRun", "stepsSingle",
-                                "thrMoves", "cycThrMove", "runCapZero", "tplTableHits"};
+                                "thrMoves", "cycThrMove", "runCapZero", "tplTableHits",
+                                "sortsCross50", "pivotArith", "sortsAppend50", "appendClosed", "pivotArithDiff",
+                                "cycPivot", "cycRegather", "cycCrossQuick"};
   static_assert(sizeof(names) / sizeof(names[0]) == CT_NCOUNTERS, "one name per counter");
   for (int i = 0; i < CT_NCOUNTERS; i++) o += std::string(i ? "," : "") + "\"" + names[i] + "\":" + std::to_string(r->counters[i]);
   o += ",\"tplTable\":" + std::to_string(r->tplTable ? 1 : 0) + ",\"tplClasses\":" + std::to_string(r->tplClasses) +

@@ -407,8 +407,20 @@ enum Counter {
   CT_KIND,
   CT_KIND_END = CT_KIND + 9,
   CT_TPL_TABLE_HITS = CT_KIND_END,  // LEAN Solve NewNodeClaims that missed the memo and took k_fresh_claims' record (KS_TPL_TABLE)
-  CT_NCOUNTERS
+  // LEAN Solve claim re-sorts by origin (KS_PIVOT_ARITH, KS_APPEND_CLOSED).  The "eligible" counts do not depend on
+  // the switches; a "taken" count is 0 with its switch off
+  CT_SORT_CROSS50,    // re-sorts after a count increment at a known position (pos >= 0) with n >= 50
+  CT_PIVOT_ARITH,     // ... of those, the ones whose choosePivot hint and pivot came from n and pos, no sample read
+  CT_SORT_APPEND50,   // re-sorts after an appended claim with n >= 50 and a descent at the last position
+  CT_APPEND_CLOSED,   // ... of those, the ones done by the appended claim's closed form
+  CT_PIVOT_ARITH_DIFF,  // diagnostic build (-DKS_PIVOT_ARITH_CHECK=1): re-sorts with a descent at pos whose sampled hint
+                        // or pivot differs from the arithmetic form (0)
+  // diagnostic build: sub-phases inside cycSort and cycCross (cycles): w_choose_pivot at the top frame, sort_claims'
+  // regather of s_ptpl / s_phead, the crossing loop's quick re-tests
+  CT_CYC_RESORT,
+  CT_NCOUNTERS = CT_CYC_RESORT + 3
 };
+enum ResortSub { ZS_PIVOT = 0, ZS_REGATHER, ZS_CROSS_QUICK };
 enum SplitSub { YS_TPL_CAND = 0, YS_TPL_FEAS, YS_TPL_FILTER, YS_TPL_THR, YS_LOG_LOAD, YS_LOG_STORE };
 enum KindSub { KD_CYC_OPEN = 0, KD_CYC_RUN, KD_CYC_SINGLE, KD_N_OPEN, KD_N_RUN, KD_N_SINGLE, KD_THR_MOVES, KD_CYC_THR_MOVE, KD_CAP_ZERO };
 

@@ -30,6 +30,10 @@ hipError_t launch_sims_split(const KsDev& D, const KsWork* works_dev, int nsims,
 int run_fuse_build();  // the KS_RUN_FUSE the LEAN Solve was compiled with (ks_problem_inspect reports it)
 int sort_leaf_build();     // ... and KS_SORT_LEAF ("sortLeaf"), KS_CLOSED_SHIFT ("closedShift")
 int closed_shift_build();
+int pivot_arith_build();   // KS_PIVOT_ARITH ("pivotArith"), its self-check KS_PIVOT_ARITH_CHECK ("pivotArithCheck"),
+int pivot_arith_check_build();  // KS_CROSS_QUICK_FROM ("crossQuickFrom")
+int cross_quick_from_build();
+int append_closed_build();  // KS_APPEND_CLOSED ("appendClosed")
 int tpl_masks_build();     // KS_TPL_MASKS ("tplMasks"), KS_LOG_RUNS ("logRuns")
 int log_runs_build();
 int sort_regs_build();     // KS_SORT_REGS ("sortRegs") and its n <= 64 form, KS_SORT_REGS_N64 ("sortRegsN64")
@@ -42,7 +46,8 @@ int tpl_table_build();     // KS_TPL_TABLE ("tplTableBuild") and its self-check,
 int tpl_table_check_build();
 // k_fresh_claims (ks_solve.hip): ncls x NTPL records into the fresh-NodeClaim block at blk (device), R 3 or 4
 hipError_t launch_fresh_claims(const KsDev& D, const KsWork* works, const Plan& pl, uint32_t* blk, int ncls, hipStream_t st);
-// ks_claim_sort_probe's kernel (ks_solve.hip): device pointers, how [64] (how, path); n <= kProbeMaxN, R 3 or 4
+// ks_claim_sort_probe's kernel (ks_solve.hip): device pointers, how [64] (how, path, the appended claim's closed
+// form ran); mode 2: the append origin told (ks_claim_sort_probe_append); n <= kProbeMaxN, R 3 or 4
 hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,
                             const int64_t* chead, int32_t* ptpl, int64_t* phead, int32_t* how, hipStream_t st);
 // frontTotal: KsDev::frontTotal, the Pareto-front positions a LEAN Solve keeps in LDS

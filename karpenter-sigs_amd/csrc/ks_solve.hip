@@ -62,11 +62,39 @@
 #define KS_RUN_FUSE 0
 #endif
 // LEAN Solve: 1 moves the closed form's block by shifting the four position arrays from registers, its reads
-// issued together (0: pis_move, then a regather of s_ptpl / s_phead through the claims).  Measured on C2 at -0.066 ms
-// of 6.74 (-0.030 before its reads were made unconditional), under the round's margin of three spreads, 0.075 ms
-// (DESIGN §7): off
+// issued together (0: pis_move, then a regather of s_ptpl / s_phead through the claims).  Round 11 measured it on C2
+// at -0.066 ms of 6.74 with choosePivot's samples issued inside it, under that round's margin: off.  On top of
+// KS_PIVOT_ARITH (no samples: K, the next key and 256 keys in one batch) it measured -0.179 ms of 5.476, every run
+// faster, against a margin of 0.060 ms (round 17): on
 #ifndef KS_CLOSED_SHIFT
-#define KS_CLOSED_SHIFT 0
+#define KS_CLOSED_SHIFT 1
+#endif
+// LEAN Solve: 1 takes choosePivot's hint at the top frame of a re-sort after a count increment at `pos` from n and
+// pos alone, with no sample read: for n >= 50 and a confirmed descent at pos the hint is "increasing" exactly when
+// pos is none of l-1, l, 2l-1, 2l, 3l-1, 3l (l = n/4), and the pivot is then 2l (DESIGN §3,
+// tests/test_pivot_arith_model.py).  Anything else samples as before (0: always samples).
+// KS_PIVOT_ARITH_CHECK=1: a diagnostic build that samples as well and counts disagreements (`pivotArithDiff`)
+#ifndef KS_PIVOT_ARITH
+#define KS_PIVOT_ARITH 1
+#endif
+#ifndef KS_PIVOT_ARITH_CHECK
+#define KS_PIVOT_ARITH_CHECK 0
+#endif
+// LEAN Solve: 1 lets a run that crossed by the closed form re-test claim_quick only on the entries its claim was
+// lifted over, [old position, new position), when no position of this step passed the quick test and failed
+// claim_full (0: every position before the new one).  Measured on C2 at +0.018 ms of 5.297 (-0.030 ms of 5.45 in a
+// session without the register shift), under the margins of 0.057 and 0.051 ms (round 17): off
+#ifndef KS_CROSS_QUICK_FROM
+#define KS_CROSS_QUICK_FROM 0
+#endif
+// LEAN Solve: 1 re-sorts after an appended claim at n >= 50 by its closed form: the new entry goes to the end of the
+// counts not above its own, the entries behind move one place right in all four position arrays (0: choosePivot,
+// partialInsertionSort and a regather, as before).  Measured on C2 at -0.124 ms of 5.297, every run faster,
+// against a margin of 0.075 ms.  It ships off all the same: these re-sorts then are neither closed-form (sortsClosed,
+// pinned) nor general ones on the register copy, and tests/test_sort_regs_gpu.py pins sortsRegs + sortRegsOver ==
+// sortsWithDescent - sortsClosed (round 17).  scripts/variant_check.sh runs a build with it on
+#ifndef KS_APPEND_CLOSED
+#define KS_APPEND_CLOSED 0
 #endif
 #ifndef KS_SORT_CLOSED  // the claim re-sort's closed form at a single count crossing: 0 off, 1 LEAN Solve, 2 every Solve
 #define KS_SORT_CLOSED 1
@@ -282,6 +310,8 @@ __device__ __forceinline__ void lds_copy(T KS_L* dst, const T KS_G* src, int n) 
 #define XPH_COUNT(slot) xcyc[slot] += 1
 #define YPH_END(v, slot) ycyc[slot] += __builtin_amdgcn_s_memtime() - v  // SS_TPL_DERIVE / SS_LOG split (Solver member, CT_CYC_SPLIT)
 #define SYPH_END(o, v, slot) o.ycyc[slot] += __builtin_amdgcn_s_memtime() - v  // (from k_solve)
+#define ZPH_END(v, slot) zcyc[slot] += __builtin_amdgcn_s_memtime() - v  // inside cycSort / cycCross (Solver member, CT_CYC_RESORT)
+#define SZPH_END(o, v, slot) o.zcyc[slot] += __builtin_amdgcn_s_memtime() - v  // (from k_solve)
 #define PH_WAIT_LOADS() __builtin_amdgcn_s_waitcnt(0x0f70)  // vmcnt(0): a stamp after it has waited for the loads
 #else
 #define PH_BEGIN(v)
@@ -294,6 +324,8 @@ __device__ __forceinline__ void lds_copy(T KS_L* dst, const T KS_G* src, int n) 
 #define XPH_COUNT(slot)
 #define YPH_END(v, slot)
 #define SYPH_END(o, v, slot)
+#define ZPH_END(v, slot)
+#define SZPH_END(o, v, slot)
 #define PH_WAIT_LOADS()
 #endif
 
@@ -654,6 +686,9 @@ constexpr int kTdw = 256, kTdwKeys = 4;
 struct ClaimSort {
   LI32 s_order;         // [KO] s.newNodeClaims as claim ids
   LI32 s_okey;          // [KO] len(Pods) of the claim at each position
+#ifdef KS_PHASE_STATS
+  uint64_t pivcyc = 0;  // cycles of w_choose_pivot inside closed_crossing (added to cycPivot)
+#endif
   // --- s.newNodeClaims re-sort (scheduler.go:247) --------------------------------------------------
   // Called only when the array is not non-decreasing (a non-decreasing array is provably left
   // untouched by pdqsort).  Lane 0 replays Go's pdqsort_func; the position-indexed quick-reject
@@ -752,6 +787,16 @@ struct ClaimSort {
     }
     hint = swaps == 0 ? 1 : (swaps == 12 ? 2 : 0);
     return j;
+  }
+  // KS_PIVOT_ARITH: is `pos` or pos + 1 inside one of choosePivot's three sample triples of [0, n), n >= 50?  The
+  // triples are {l-1, l, l+1}, {2l-1, 2l, 2l+1}, {3l-1, 3l, 3l+1}, l = n/4 >= 12: a descent between pos and pos + 1
+  // is seen by a median network exactly when both lie in one triple.  On an array non-decreasing but for that
+  // descent, every other comparison of choosePivot finds its pair in order (the three medians are then the middle
+  // samples l, 2l, 3l, whose keys the increment did not lift above a later sample's): no swap, hint "increasing",
+  // pivot 2l.
+  static __device__ __forceinline__ bool pivot_sampled(int n, int pos) {
+    const int l = n / 4, e = pos - (l - 1);
+    return e == 0 || e == 1 || e == l || e == l + 1 || e == 2 * l || e == 2 * l + 1;
   }
   // partialInsertionSort_func(data, 0, n) of Go 1.21 (zsortfunc.go), wave-parallel: each of its <= 5
   // steps finds the next descent by ballot, swaps the pair, then moves the smaller entry left past
@@ -953,8 +998,10 @@ struct ClaimSort {
   // The reads that do not depend on each other are issued together: the nine samples, K, the next key and the first
   // 256 keys past pos; then the moved entries of the four arrays, 256 positions per read and write batch, low
   // positions first (a batch writes one place below what it read: below itself, or onto pos, read before).
-  template <int R>
-  __device__ __forceinline__ int closed_crossing(int n, int pos, LI32 ptpl, LI64 phead, int& hint, int& pv) {
+  // PA (KS_PIVOT_ARITH): with the descent at pos confirmed and pos off the sample triples the hint and the pivot are
+  // arithmetic (`arith`) and the nine samples are not read: the batch is K, the next key and the 256 keys.
+  template <int R, bool PA>
+  __device__ __forceinline__ int closed_crossing(int n, int pos, LI32 ptpl, LI64 phead, int& hint, int& pv, bool& arith) {
     const bool cand = pos >= 0 && n >= 50 && pos + 1 < n;
     const int pc = cand ? pos : 0;  // (n > 12: the reads stay inside the array for any pos)
     const int K = s_okey[pc], nx = s_okey[pc + 1];
@@ -965,8 +1012,21 @@ struct ClaimSort {
       const int q = pc + 1 + u * kWave + lane(), k = s_okey[q < n ? q : n - 1];
       kq[u] = q < n ? k : INT32_MAX;
     }
-    pv = w_choose_pivot(0, n, hint);
-    if (!cand || hint != 1 || !ub(K > nx)) return -1;
+    arith = false;
+    if constexpr (PA) arith = cand && !pivot_sampled(n, pc) && ub(K > nx);
+    if (arith) {
+      hint = 1;
+      pv = n / 4 * 2;
+    } else {
+#ifdef KS_PHASE_STATS
+      const uint64_t tpv = __builtin_amdgcn_s_memtime();
+#endif
+      pv = w_choose_pivot(0, n, hint);
+#ifdef KS_PHASE_STATS
+      pivcyc += __builtin_amdgcn_s_memtime() - tpv;  // (the stamp also waits for the key batch issued above)
+#endif
+      if (!cand || hint != 1 || !ub(K > nx)) return -1;
+    }
     int t = 0;
     bool end = false;
 #pragma unroll
@@ -1029,6 +1089,58 @@ struct ClaimSort {
     for (int r = 0; r < R; r++) phead[(int64_t)to * R + r] = h0[r];
     wsync();
     return t;
+  }
+  // The closed form of a re-sort after an appended claim (KS_APPEND_CLOSED), n >= 50: non-decreasing on [0, n-1),
+  // key[n-1] < key[n-2].  choosePivot's samples end at 3(n/4) + 1 < n - 1 and find the array increasing;
+  // partialInsertionSort swaps the last pair, walks the new entry left past every greater key and meets no second
+  // descent (tests/test_pivot_arith_model.py).  With p = #{q < n-1 : key[q] <= key[n-1]}, the first p entries of a
+  // sorted prefix, [p, n-1) moves one place right in s_okey, s_order, ptpl and phead ([.][R]), high chunk first and
+  // each chunk read before it is written, and the new claim's entries go to p.  Returns p, or -1 with the arrays
+  // untouched when the last entry is not below its neighbour.
+  template <int R>
+  __device__ __forceinline__ int append_closed(int n, LI32 ptpl, LI64 phead) {
+    const int K = s_okey[n - 1], pk = s_okey[n - 2];  // uniform addresses: every lane holds the new claim's entries
+    const int v0 = s_order[n - 1], tp0 = ptpl[n - 1];
+    int64_t h0[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) h0[r] = phead[(int64_t)(n - 1) * R + r];
+    if (!ub(K < pk)) return -1;
+    int p = 0;
+    for (int base = 0; base < n - 1; base += kWave) {
+      const int q = base + lane();
+      const uint64_t m = wballot(q < n - 1 && s_okey[q] <= K);
+      p += popc64(m);
+      if (m != ~0ull) break;
+    }
+    wsync();
+    for (int hi = n - 1; hi > p; hi -= kWave) {
+      const int lo = hi - kWave > p ? hi - kWave : p, j = lo + lane();
+      int k = 0, v = 0, tp = 0;
+      int64_t h[R];
+      if (j < hi) {
+        k = s_okey[j];
+        v = s_order[j];
+        tp = ptpl[j];
+#pragma unroll
+        for (int r = 0; r < R; r++) h[r] = phead[(int64_t)j * R + r];
+      }
+      wsync();
+      if (j < hi) {
+        s_okey[j + 1] = k;
+        s_order[j + 1] = v;
+        ptpl[j + 1] = tp;
+#pragma unroll
+        for (int r = 0; r < R; r++) phead[(int64_t)(j + 1) * R + r] = h[r];
+      }
+      wsync();
+    }
+    s_okey[p] = K;  // wave-wide stores of uniform values (see commit_claim)
+    s_order[p] = v0;
+    ptpl[p] = tp0;
+#pragma unroll
+    for (int r = 0; r < R; r++) phead[(int64_t)p * R + r] = h0[r];
+    wsync();
+    return p;
   }
   // GoSortExactT::run with the whole wave: frames live one per lane (lane k = stack slot k), the
   // partitions, reversals and partialInsertionSorts run wave-parallel, and so do the frames of <= 12 entries
@@ -1308,6 +1420,7 @@ struct Solver : ClaimSort {
   uint64_t ecyc[3] = {0, 0, 0};  // the exact re-sorts' cycles by size (CT_CYC_EXACT_BY_N)
   mutable uint64_t ycyc[6] = {0, 0, 0, 0, 0, 0};  // SS_TPL_DERIVE and SS_LOG split (SplitSub)
   mutable uint64_t kcyc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // the steps by kind, threshold moves, empty runs (KindSub)
+  mutable uint64_t zcyc[3] = {0, 0, 0};  // inside cycSort and cycCross: pivot samples, regather, quick re-tests (ResortSub)
 #endif
 
   __device__ Solver(const KsDev& D_, const KsWork KS_C& W_, const Plan& p_) : D(D_), d(D_.d), W(W_), pl(p_) {}
@@ -3069,7 +3182,21 @@ struct Solver : ClaimSort {
   int sortsRegs = 0, sortRegsOver = 0, sortRegsBail = 0;  // general re-sorts finished from registers / too large for
                                                           // the copy / abandoned on a failed invariant (0)
   int64_t shiftDiff = 0;  // diagnostic build: moved entries whose shifted s_ptpl / s_phead differ from a regather
-  __device__ __forceinline__ int sort_claims(int n, int pos, int& npos) {
+  // the top frame's hint and pivot from n and pos alone (KS_PIVOT_ARITH; the LEAN Solve, where pos is tracked)
+  static constexpr bool PIVOT_ARITH = KS_PIVOT_ARITH && SORT_CLOSED && LEAN;
+  // (their counters are members of the LEAN Solve alone: the other instantiations' Solver keeps its layout)
+  struct ResortCtr {
+    int cross50 = 0, arith = 0;        // re-sorts with pos >= 0 and n >= 50 / those decided without samples
+    int append50 = 0, appClosed = 0;   // appended-claim re-sorts with n >= 50 / those taken by the closed form
+    int64_t diff = 0;  // diagnostic build (KS_PIVOT_ARITH_CHECK): re-sorts whose sampled hint or pivot differs
+  };
+  struct NoResortCtr {};
+  static constexpr bool RESORT_CTR = SORT_CLOSED && LEAN;
+  [[no_unique_address]] std::conditional_t<RESORT_CTR, ResortCtr, NoResortCtr> rsc;
+  // the appended claim's re-sort by its closed form (KS_APPEND_CLOSED; the shift keeps R resources in registers)
+  static constexpr bool APPEND_CLOSED = KS_APPEND_CLOSED && SORT_CLOSED && LEAN && RT > 0;
+  // `app`: the descent is an appended claim's (try_templates left it; pos is -1)
+  __device__ __forceinline__ int sort_claims(int n, int pos, int& npos, bool app = false) {
     int tlo = n, thi = -1, pivot = -1;
     bool done = false;
     PH_BEGIN(tsc);
@@ -3077,12 +3204,57 @@ struct Solver : ClaimSort {
     if (n <= 12) XPH_COUNT(SS_SORTS_LE12);
     else if (n < 50) XPH_COUNT(SS_SORTS_LT50);
 #endif
-    bool closed = false, shifted = false;
+    bool closed = false, shifted = false, appc = false;
     npos = -1;
-    if (n > 12) {  // pdqsort_func's top-level frame: choosePivot (reads only), then partialInsertionSort
+    if constexpr (RESORT_CTR) rsc.append50 += app && n >= 50 ? 1 : 0;
+    if constexpr (APPEND_CLOSED) {
+      if (app && n >= 50) {
+        const int p = append_closed<RM>(n, s_ptpl, s_phead);
+        if (p >= 0) {  // SORT_FAST with partialInsertionSort's span; the four arrays moved: nothing to regather
+          tlo = p;
+          thi = n - 1;
+          done = shifted = appc = true;
+          rsc.appClosed++;
+        }
+      }
+    }
+    if (n > 12 && !appc) {  // pdqsort_func's top-level frame: choosePivot (reads only), then partialInsertionSort
       int hint = 0, pv = 0, ts = -1;
-      if constexpr (CLOSED_SHIFT) ts = closed_crossing<RM>(n, pos, s_ptpl, s_phead, hint, pv);
-      else pv = w_choose_pivot(0, n, hint);
+      if constexpr (RESORT_CTR) rsc.cross50 += pos >= 0 && n >= 50 ? 1 : 0;
+#if KS_PIVOT_ARITH_CHECK
+      if constexpr (RESORT_CTR) {  // both forms, on the array as the re-sort meets it
+        if (pos >= 0 && n >= 50 && pos + 1 < n && ub(s_okey[pos] > s_okey[pos + 1])) {
+          int hs = 0;
+          const int ps = w_choose_pivot(0, n, hs);
+          const bool off = !pivot_sampled(n, pos);
+          rsc.diff += (hs == 1) != off || (off && ps != n / 4 * 2) ? 1 : 0;
+        }
+      }
+#endif
+      if constexpr (CLOSED_SHIFT) {
+        bool arith = false;
+        ts = closed_crossing<RM, PIVOT_ARITH>(n, pos, s_ptpl, s_phead, hint, pv, arith);
+        rsc.arith += arith ? 1 : 0;
+      } else if constexpr (PIVOT_ARITH) {
+        // the hint by arithmetic: closed_move confirms the descent (-1: the samples, as before)
+        int t = -1;
+        if (pos >= 0 && n >= 50 && pos + 1 < n && !pivot_sampled(n, pos)) t = closed_move(n, pos);
+        if (t >= 0) {
+          pivot = n / 4 * 2;
+          tlo = pos;
+          thi = npos = pos + t;
+          done = closed = true;
+          rsc.arith++;
+        } else {
+          PH_BEGIN(tpv);
+          pv = w_choose_pivot(0, n, hint);
+          ZPH_END(tpv, ZS_PIVOT);
+        }
+      } else {
+        PH_BEGIN(tpv);
+        pv = w_choose_pivot(0, n, hint);
+        ZPH_END(tpv, ZS_PIVOT);
+      }
       if (hint == 1) {
         pivot = pv;
         if (ts >= 0) {  // s_ptpl and s_phead moved with their claims: nothing to regather
@@ -3090,7 +3262,9 @@ struct Solver : ClaimSort {
           thi = npos = pos + ts;
           done = closed = shifted = true;
         }
-        if constexpr (SORT_CLOSED && !CLOSED_SHIFT) {
+        // (with the arithmetic hint this cannot succeed: off the sample positions closed_move has run and found no
+        // descent at pos, on them a descent at pos makes the sampled hint something else)
+        if constexpr (SORT_CLOSED && !CLOSED_SHIFT && !PIVOT_ARITH) {
           if (pos >= 0 && n >= 50 && pos + 1 < n) {
             const int t = closed_move(n, pos);
             if (t >= 0) {
@@ -3102,7 +3276,7 @@ struct Solver : ClaimSort {
         }
       }
     }
-    if (!closed) {
+    if (!closed && !appc) {
       // (out of line in the LEAN Solve, whose closed form leaves this the rare path; the other instantiations
       // keep it inlined, as measured before)
       const uint32_t g = KS_SORT_OUTLINE && LEAN && !SIM ? claim_sort_general_out(s_okey, s_order, n, pivot)
@@ -3135,6 +3309,7 @@ struct Solver : ClaimSort {
     }
 #endif
     if (!shifted) {
+      PH_BEGIN(trg);
       for (int j = tlo + lane(); j <= thi; j += kWave) {
         const int c = s_order[j];
         const bool inl = c < pl.KL;
@@ -3145,6 +3320,7 @@ struct Solver : ClaimSort {
         }
       }
       wsync();
+      ZPH_END(trg, ZS_REGATHER);
     }
     algbytes += (int64_t)(thi - tlo + 1) * (8 + 16 * R());
 #ifdef KS_PHASE_STATS
@@ -3761,6 +3937,10 @@ int tpl_masks_build() { return KS_TPL_MASKS; }
 int log_runs_build() { return KS_LOG_RUNS && KS_CLAIM_RUNS; }
 int sort_leaf_build() { return KS_SORT_LEAF && !KS_SORT_LANE0; }
 int closed_shift_build() { return KS_CLOSED_SHIFT && KS_SORT_CLOSED; }
+int pivot_arith_build() { return KS_PIVOT_ARITH && KS_SORT_CLOSED; }
+int pivot_arith_check_build() { return KS_PIVOT_ARITH_CHECK && KS_SORT_CLOSED; }
+int append_closed_build() { return KS_APPEND_CLOSED && KS_SORT_CLOSED; }
+int cross_quick_from_build() { return KS_CROSS_QUICK_FROM && KS_SORT_CLOSED && KS_RUN_CROSS && KS_CLAIM_RUNS && !KS_RUN_FUSE; }
 int sort_regs_build() { return KS_SORT_REGS != 0 && KS_SORT_OUTLINE; }
 int sort_regs_n64_build() { return sort_regs_build() && KS_SORT_REGS_N64; }
 int cap_bound_build() { return KS_CAP_BOUND && KS_CLAIM_RUNS; }
@@ -3770,8 +3950,9 @@ int run_chain_build() { return KS_RUN_CHAIN && KS_CLAIM_RUNS; }
 // Test / diagnostic kernel (ks_claim_sort_probe): Solver::sort_claims' logic on arrays of the caller's choosing,
 // one wave, no Solve.  keys / order [n] are loaded into LDS with the position arrays ptpl / phead gathered from the
 // claim tables ctpl [n] / chead [n][R] (by claim id); mode 0 sorts as for an appended claim (pos -1), mode 1 as
-// after a count increment at pos, taking the closed form where sort_claims does; all four arrays are written back
-// with how it was done (Solver::SORT_*).
+// after a count increment at pos, taking the closed form where sort_claims does, mode 2 as for an appended claim
+// that sort_claims is told of (`app`: KS_APPEND_CLOSED); all four arrays are written back with how it was done
+// (Solver::SORT_*).
 template <int R>
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_claim_sort_probe(
     int32_t* keys, int32_t* order, int n, int mode, int pos, const int32_t* ctpl, const int64_t* chead, int32_t* ptpl,
@@ -3798,17 +3979,33 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_claim_sor
   }
   wsync();
   gather(0, n - 1);
-  if (mode == 0) pos = -1;
+  if (mode != 1) pos = -1;
   int tlo = n, thi = -1, pivot = -1, res = 1;
-  bool closed = false;
-  if (n > 12) {
+  bool closed = false, appc = false;
+  if (KS_APPEND_CLOSED && KS_SORT_CLOSED && mode == 2 && n >= 50) {  // sort_claims' `app`
+    appc = cs.append_closed<R>(n, s_ptpl, s_phead) >= 0;  // (all four arrays moved: nothing to regather)
+    if (appc) res = 0;
+  }
+  if (n > 12 && !appc) {
     int hint = 0, pv = 0, ts = -1;
-    if (KS_CLOSED_SHIFT && KS_SORT_CLOSED) ts = cs.closed_crossing<R>(n, pos, s_ptpl, s_phead, hint, pv);
-    else pv = cs.w_choose_pivot(0, n, hint);
+    bool arith = false;
+    constexpr bool PA = KS_PIVOT_ARITH && KS_SORT_CLOSED;
+    if (KS_CLOSED_SHIFT && KS_SORT_CLOSED) ts = cs.closed_crossing<R, PA>(n, pos, s_ptpl, s_phead, hint, pv, arith);
+    else {
+      if (PA && pos >= 0 && n >= 50 && pos + 1 < n && !ClaimSort::pivot_sampled(n, pos)) {
+        const int t = cs.closed_move(n, pos);
+        if (t >= 0) {
+          arith = closed = true;
+          tlo = pos;
+          thi = pos + t;
+        }
+      }
+      if (!arith) pv = cs.w_choose_pivot(0, n, hint);
+    }
     if (hint == 1) {
       pivot = pv;
       if (ts >= 0) closed = true;  // (nothing to regather)
-      else if (KS_SORT_CLOSED && !KS_CLOSED_SHIFT && pos >= 0 && n >= 50 && pos + 1 < n) {
+      else if (KS_SORT_CLOSED && !KS_CLOSED_SHIFT && !PA && pos >= 0 && n >= 50 && pos + 1 < n) {
         const int t = cs.closed_move(n, pos);
         if (t >= 0) {
           closed = true;
@@ -3821,7 +4018,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_claim_sor
   int path = 0;  // the general re-sort's (KS_SORT_REGS): 1 finished on the register copy, 2 abandoned on a failed
                  // invariant, 3 more entries than the copy holds (2 and 3: the LDS code sorted)
   if (closed) res = 2;
-  else {
+  else if (!appc) {
     const uint32_t g = claim_sort_general<true, true>(cs.s_okey, cs.s_order, n, pivot);
     tlo = (int)(g & 0x7fff);
     thi = (int)(g >> 15 & 0x7fff) - 1;
@@ -3836,7 +4033,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_claim_sor
     ptpl[j] = s_ptpl[j];
     for (int r = 0; r < R; r++) phead[(int64_t)j * R + r] = s_phead[(int64_t)j * R + r];
   }
-  how[lane()] = lane() == 1 ? path : res;  // [kWave]: how, and in word 1 the path
+  how[lane()] = lane() == 1 ? path : lane() == 2 ? (int)appc : res;  // [kWave]: how, in word 1 the path, in word 2
+                                                                     // whether the appended claim's closed form ran
 }
 // n <= kProbeMaxN positions, R 3 or 4 (the LEAN Solve's resource counts); the arrays are device pointers
 hipError_t claim_sort_probe(int32_t* keys, int32_t* order, int n, int mode, int pos, int R, const int32_t* ctpl,

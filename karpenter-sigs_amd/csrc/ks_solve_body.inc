@@ -287,6 +287,7 @@
   // tracked (sort_claims' closed form, KS_SORT_CLOSED)
   constexpr bool SORTC = Solver<RT, TL, SIM, TOPO, LEAN>::SORT_CLOSED;
   int dpos = -1;
+  bool dapp = false;  // ... and that it is an appended claim's (try_templates left it)
   int64_t sortsClosed = 0;
   bool pushed = false;  // a failed pod was pushed back since the last window refill
   // no pod was pushed back yet (refill reads the pods' first states directly); a probe re-run from carried pods
@@ -887,12 +888,13 @@
       if (!U(srt)) {
         const int64_t ab = S.algbytes;
         int npos;
-        const int how = S.sort_claims(nclaims, SORTC ? dpos : -1, npos);
+        const int how = S.sort_claims(nclaims, SORTC ? dpos : -1, npos, SORTC && dapp);
         exact += how == S.SORT_EXACT;
         sortsClosed += how == S.SORT_CLOSED_FORM;
         slow++;
         srt = true;
         dpos = -1;
+        dapp = false;
         sortB += S.algbytes - ab;
       }
       PH_END(t2, 2);
@@ -1124,8 +1126,15 @@
                         // the first position passing the quick test; the claim's position: the closed form
                         // knows it, any other sort leaves it to be looked up in s_order
                         int fq = -1, np = UI(npos);
+                        PH_BEGIN(tcq);
                         if (SORTC && np >= 0) {
-                          for (int base = 0; base < np && fq < 0; base += kWave) {
+                          // KS_CROSS_QUICK_FROM: the positions before the claim's old one hold claims this step did
+                          // not touch, and the same pod failed the quick test on each of them (this step's scan, or
+                          // an earlier crossing's re-test) -- unless one passed it and failed claim_full, whose
+                          // recompute_max rewrote its headroom (stepFF).  Only the entries lifted over can newly
+                          // stand before the claim: [old pos, new pos)
+                          const int q0 = KS_CROSS_QUICK_FROM && LEAN && stepFF == 0 ? pos : 0;
+                          for (int base = q0; base < np && fq < 0; base += kWave) {
                             const int j = base + lane();
                             const uint64_t mq = wballot(j < np && S.claim_quick(j, s, sflags, toltpl, pod));
                             if (mq) fq = base + ctz64(mq);
@@ -1143,6 +1152,7 @@
                           }
                           np = UI(np);
                         }
+                        SZPH_END(S, tcq, ZS_CROSS_QUICK);
                         if (np < 0) {  // unreachable: s_order is a permutation of the claims
                           err = KE_STACK;
                           qlen = 0;
@@ -1285,6 +1295,7 @@
       hostCtr = UI(hostCtr);
       srt = U(srt);
       dpos = -1;  // a descent left here is an appended claim's
+      dapp = !srt;
       if (r < 0) {
         err = KE_CLAIM_CAP;
         if constexpr (decltype(S)::TPL_TABLE_CHECK) err = r == -2 ? KE_TPL_TABLE : KE_CLAIM_CAP;
@@ -1409,6 +1420,13 @@
       W.counters[CT_SORT_REGS_BAIL] = S.sortRegsBail;
       W.counters[CT_SORT_REGS_OVER] = S.sortRegsOver;
     }
+    if constexpr (decltype(S)::RESORT_CTR) {  // (k_init zeroed them: the other instantiations' code stays as it was)
+      W.counters[CT_SORT_CROSS50] = S.rsc.cross50;
+      W.counters[CT_PIVOT_ARITH] = S.rsc.arith;
+      W.counters[CT_SORT_APPEND50] = S.rsc.append50;
+      W.counters[CT_APPEND_CLOSED] = S.rsc.appClosed;
+      W.counters[CT_PIVOT_ARITH_DIFF] = S.rsc.diff;
+    }
     if constexpr (CAPB) W.counters[CT_CAP_BOUND_SKIPS] = S.capBoundSkips;
     if constexpr (CHAINB) W.counters[CT_CHAIN_PODS] = chainPods;
     if constexpr (decltype(S)::THR_BATCH) {
@@ -1426,6 +1444,8 @@
     W.counters[CT_CLOSED_SHIFT_DIFF] = S.shiftDiff;
     for (int i = 0; i < 6; i++) W.counters[CT_CYC_SPLIT + i] = (int64_t)S.ycyc[i];
     for (int i = 0; i < 9; i++) W.counters[CT_KIND + i] = (int64_t)S.kcyc[i];
+    for (int i = 0; i < 3; i++) W.counters[CT_CYC_RESORT + i] = (int64_t)S.zcyc[i];
+    W.counters[CT_CYC_RESORT + ZS_PIVOT] += (int64_t)S.pivcyc;  // the samples taken inside closed_crossing
 #endif
   }
   if constexpr (SIM) S.sim_record(P, nclaims, hostCtr, allSched, err, !ident, anyRelaxed);

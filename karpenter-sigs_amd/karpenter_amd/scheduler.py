@@ -220,6 +220,29 @@ def claim_sort_probe(keys, order, claim_tpl, claim_head, mode=0, pos=-1, device=
     return k, o, pt, ph, how.value
 
 
+def claim_sort_probe_append(keys, order, claim_tpl, claim_head, device=0):
+    """Test / diagnostic (ks_claim_sort_probe_append): the re-sort after a claim appended behind greater counts, the
+    origin told to the kernel as the Solve tells it; device=-1: Go's pdqsort_func on the host.  Returns (keys, order,
+    ptpl, phead, how, taken), taken 1 when the appended claim's closed form ran."""
+    import numpy as np
+
+    k = np.array(keys, dtype=np.int32)
+    o = np.array(order, dtype=np.int32)
+    ct = np.ascontiguousarray(claim_tpl, dtype=np.int32)
+    ch = np.ascontiguousarray(claim_head, dtype=np.int64)
+    n = len(k)
+    assert len(o) == n and len(ct) == n and ch.ndim == 2 and ch.shape[0] == n
+    r = ch.shape[1]
+    pt = np.zeros(n, dtype=np.int32)
+    ph = np.zeros((n, r), dtype=np.int64)
+    how, taken = ctypes.c_int(-1), ctypes.c_int(0)
+    lib().ks_claim_sort_probe_append.argtypes = ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6 +
+                                                 [ctypes.POINTER(ctypes.c_int)] * 2)
+    _check(lib().ks_claim_sort_probe_append(device, n, r, k.ctypes.data, o.ctypes.data, ct.ctypes.data, ch.ctypes.data,
+                                            pt.ctypes.data, ph.ctypes.data, ctypes.byref(how), ctypes.byref(taken)))
+    return k, o, pt, ph, how.value, taken.value
+
+
 def cluster_state(cluster):
     """Cluster-state accounting (pkg/controllers/state, cluster.go:220-512 + statenode.go:110-333):
     the StateNode accessor values the informers converge to for {"nodeClaims", "nodes", "pods"}, as a

@@ -31,7 +31,9 @@ for k in ["cycPop", "cycNodes", "cycNodeCommit", "cycSort", "cycQuick", "cycFull
           # front test; a run's queue loads past the window, its log entries (or its record)
           "cycTplCand", "cycTplFeas", "cycTplFilter", "cycTplThr", "cycLogLoad", "cycLogStore",
           # the exact re-sorts by size (inside cycSortExact)
-          "cycSortExactLe12", "cycSortExactLt50", "cycSortExactGe50"]:
+          "cycSortExactLe12", "cycSortExactLt50", "cycSortExactGe50",
+          # inside cycSort: choosePivot's samples at the top frame, the regather; inside cycCross: the quick re-tests
+          "cycPivot", "cycRegather", "cycCrossQuick"]:
     if k in st:
         print("%-16s %6.1f%%  %8.1f cyc/pod" % (k, 100.0 * st[k] / tot, st[k] / n))
 closed, exact = st["sortsClosed"], st["sortsExact"]
@@ -55,6 +57,12 @@ if "stepsOpen" in st:
 if closed:
     print("cycles per closed re-sort %.0f;  closedShiftDiff %s (moved entries whose shifted value differs from a regather)" % (
         st["cycSortClosed"] / closed, st.get("closedShiftDiff", "n/a")))
+fast = st["sortsWithDescent"] - exact - closed
+if fast:
+    print("cycles per appended-claim (fast) re-sort %.0f" % (st["cycSortFast"] / fast))
+if "sortsCross50" in st:
+    print("sortsCross50 %d pivotArith %d pivotArithDiff %d;  sortsAppend50 %d appendClosed %d" % (
+        st["sortsCross50"], st["pivotArith"], st["pivotArithDiff"], st["sortsAppend50"], st["appendClosed"]))
 if exact:
     print("cycles per exact re-sort %.0f" % (st["cycSortExact"] / exact))
 print("total cyc/pod %.1f  pops %d  sorts %d slow %d  claims %d  solve_kernel_ms %.2f" % (
