@@ -42,7 +42,10 @@ typedef struct ks_solve_opts {
   int timing_only;     /* 1: do not copy results back (counters and timings only); benchmarks */
   int lds_budget;      /* bytes of LDS per Solve; 0 = automatic (tests use small budgets to force the
                           HBM-resident claim path) */
-  int reserved[3];
+  int launch_lists;    /* 1: also compute every NewNodeClaim's launch list on the device
+                          (ks_results_nodeclaim_launch); 0: no launch data, Results as without the field.
+                          Ignored with timing_only */
+  int reserved[2];
 } ks_solve_opts;
 
 /* NewScheduler equivalent: parse + encode the snapshot and upload it to HBM.  Replaces the Go
@@ -77,8 +80,14 @@ int ks_problem_check_binary(const void* buf, size_t len);
  * (count words), "tgSmall" (the prefix of small-key groups), "TK" and "topologyKeys" (the distinct topology keys in
  * key-slot order), "topologyGroups" ([key slot, domains, in the small prefix, type, hostname] per group); each plan
  * has "tcl" / "tdl" (count words / node-domain words it keeps in LDS).
+ * Launch lists: "nameRank" (per template, for each position of its instance-type list, the rank of the instance
+ * type's name in bytewise string order among all instance types: OrderByPrice's tie-break as the device reads it)
+ * and "launchListsRefusal" ("" or the message a Solve with launch_lists set fails with: a template listing two
+ * instance types of one name).
  * Diagnostics / CPU tests. */
 int ks_problem_inspect(const char* snapshot_json, size_t len, char** dims_json);
+/* The same document for a binary snapshot (what ks_problem_create_binary would load), no device. */
+int ks_problem_inspect_binary(const void* buf, size_t len, char** dims_json);
 
 /* Test and diagnostic entry: read back one of the two static feasibility tables a Solve computes before
  * k_solve.  which = 0: k_feasibility's pod-state x instance-type rows; which = 1: k_feasibility_nodes's
@@ -248,6 +257,25 @@ int ks_results_nodeclaim_requests(const ks_results* r, int i, int* n, const char
 /* NodeClaim i's Requirements after FinalizeScheduling (hostname removed, nodeclaim.go:123-128), one entry
  * per key in key order (what consolidation.go:134-188 reads from NewNodeClaims[0]). */
 int ks_results_nodeclaim_requirements(const ks_results* r, int i, int* n, const ks_requirement** reqs);
+/* NodeClaimTemplate.ToNodeClaim's launch list (nodeclaimtemplate.go:55-60) of NodeClaim i: its instance-type
+ * options in InstanceTypes.OrderByPrice order (types.go:62-79), cut to the first 100.  An option's price is its
+ * cheapest available offering that the NodeClaim's zone and capacity-type requirements allow (Offerings.Available()
+ * .Requirements(reqs).Cheapest(), types.go:147-166; a key the requirements do not hold allows every value), and
+ * math.MaxFloat64 when no offering is allowed (which the Solve's own offering filter rules out for a NodeClaim it
+ * returns); equal prices (-0.0 equals 0.0) are ordered by name, bytewise.  Computed by a kernel after the Solve
+ * when ks_solve_opts.launch_lists is set, from the claim state and the offering tables resident on the device,
+ * and checked on the host before it is handed out.
+ *   instance_types / prices: *n entries each (indices into the snapshot's instanceTypes; the price that ordered
+ *   the entry), *n = min(*n_options, 100); *n_options: len(InstanceTypeOptions).  Arrays live as long as r; any
+ *   out pointer may be NULL.
+ * KS_ERR_ARG for i out of range and for a Results whose Solve did not set launch_lists.  A Solve with launch_lists
+ * set fails with KS_ERR_UNSUPPORTED when a template lists two instance types of the same name (the order of equal
+ * keys is then sort.Slice's, not a function of the keys), and with KS_ERR_CAPACITY when a template's list is too
+ * long for the kernel's LDS (more than about 6000 instance types). */
+int ks_results_nodeclaim_launch(const ks_results* r, int i, const int32_t** instance_types, const double** prices,
+                                int* n, int* n_options);
+/* HIP-event time of the launch-list kernel of this Solve (milliseconds); 0 when it did not run. */
+double ks_results_launch_ms(const ks_results* r);
 
 /* Device time of the solve kernel(s) of the last ks_solve, measured with HIP events on the
  * stream the kernel ran on (milliseconds). */

@@ -15,6 +15,7 @@
 #include "ks_feas.h"
 #include "ks_feas_host.h"
 #include "ks_host.h"
+#include "ks_launch.h"
 #include "ks_runtime.h"
 #include "ks_sort_probe.h"
 
@@ -156,6 +157,9 @@ struct ks_results {
     int64_t host;
     std::vector<int32_t> pods, its;
     std::vector<uint32_t> rec;  // the NodeClaim's requirement record (RSW words)
+    // the launch list (ks_solve_opts.launch_lists): k_launch_lists' row after the host's check
+    std::vector<int32_t> launchIts;
+    std::vector<double> launchPrices;
     // structured accessors (ks_results_nodeclaim_requests / _requirements); the pointer arrays point
     // into the string vectors, rebuilt by bind() after every move
     std::vector<std::string> reqNames, reqQty;
@@ -197,6 +201,8 @@ struct ks_results {
   bool tplTable = false;
   int tplClasses = 0;
   float tplTableMs = 0;
+  bool hasLaunch = false;  // the Solve set launch_lists: every claim carries its launch list
+  float launchMs = 0;      // k_launch_lists by events
   // First-use rendering writes the claims' caches: serialised, so two threads reading one Results (ctypes
   // and cgo release the interpreter / scheduler around the call) render once; what a call hands out is
   // never rebuilt afterwards.
@@ -420,6 +426,7 @@ void ks_upload(ks_problem* pb, bool classes) {
   if (fnState.empty()) fnState.push_back(0);
   size_t o_fnr = put(fnrow.data(), fnrow.size() * 4);
   size_t o_fns = put(fnState.data(), fnState.size() * 4);
+  size_t o_inr = put(t.it_name_rank.data(), t.it_name_rank.size() * 4);
   // one allocation, zeroed on the device (padding and empty tables), each table copied from its host vector
   // (no host staging image of the whole problem)
   HIPCHK(hipMalloc(&pb->dbuf, a.total));
@@ -490,6 +497,7 @@ void ks_upload(ks_problem* pb, bool classes) {
   D.st_fn = (uint32_t*)pb->fnbuf;
   D.st_fnrow = (const int32_t*)(b + o_fnr);
   D.fn_state = (const int32_t*)(b + o_fns);
+  pb->nameRank = (const int32_t*)(b + o_inr);
   D.d = h.dims;
   D.keys = (const KeyMeta*)(b + o_keys);
   D.wordValid = (const uint32_t*)(b + o_wv);
@@ -792,8 +800,24 @@ static KsError claim_cap_error(const ks_problem* pb) {
   return KsError(KS_ERR_CAPACITY, "NodeClaim capacity (" + std::to_string(pb->lastKO) + " per Solve at this LDS budget) exceeded");
 }
 
-// Rebuild Results from the replica-0 workspace.
-static ks_results* collect(ks_problem* pb, const KsWork& W) {
+// Launch lists need a total order: (price, name) is one only when no template lists two instance types of the
+// same name (Go's sort.Slice is not stable, so equal keys have no defined order).  "" when every template's names
+// are unique, else the refusal naming the first template and name.
+static std::string launch_names_refusal(const Host& h) {
+  for (size_t t = 0; t < h.tpls.size(); t++) {
+    std::vector<int> ids(h.tpls[t].its.begin(), h.tpls[t].its.end());
+    std::sort(ids.begin(), ids.end(), [&](int a, int b) { return h.its[(size_t)a].name < h.its[(size_t)b].name; });
+    for (size_t i = 1; i < ids.size(); i++)
+      if (h.its[(size_t)ids[i - 1]].name == h.its[(size_t)ids[i]].name)
+        return "launch lists: template " + std::to_string(t) + " (nodepool " + go_quote(h.tpls[t].pool) +
+               ") lists two instance types named " + go_quote(h.its[(size_t)ids[i]].name) +
+               "; OrderByPrice has no defined order for them";
+  }
+  return "";
+}
+
+// Rebuild Results from the replica-0 workspace.  launch: also every claim's launch list (k_launch_lists).
+static ks_results* collect(ks_problem* pb, const KsWork& W, bool launch) {
   PhaseTimer pt("collect");
   Host& h = pb->host;
   const KsDims& d = h.dims;
@@ -812,6 +836,38 @@ static ks_results* collect(ks_problem* pb, const KsWork& W) {
   std::vector<int64_t> creq;
   std::vector<uint32_t> crs, crem, fcode;
   std::vector<int32_t> fhost;
+  // the launch lists: one kernel over the nc claims behind the Solve on the same stream, its rows downloaded with
+  // the claim arrays below (one synchronisation for all of them)
+  std::vector<LaunchRow> lrows;
+  hipEvent_t le0 = nullptr, le1 = nullptr;
+  struct EventGuard {
+    hipEvent_t &a, &b;
+    ~EventGuard() {
+      if (a) (void)hipEventDestroy(a);
+      if (b) (void)hipEventDestroy(b);
+    }
+  } eventGuard{le0, le1};
+  if (launch && nc > 0) {
+    if (nc > d.Kcap) throw KsError(KS_ERR_INTERNAL, "device state check: more NodeClaims than the workspace holds");
+    if (launch_lds_bytes(d.TW, d.RSW) > kLaunchMaxLds)
+      throw KsError(KS_ERR_CAPACITY, "launch lists: a template's instance-type list (" + std::to_string(d.maxTplIts) +
+                                         ") is too long for the kernel's LDS");
+    if ((size_t)nc > pb->launchCap) {
+      if (pb->launchBuf) HIPCHK(hipFree(pb->launchBuf));
+      pb->launchBuf = nullptr;
+      pb->launchCap = 0;
+      const size_t cap = std::max<size_t>((size_t)nc + (size_t)nc / 2, 64);
+      HIPCHK(hipMalloc(&pb->launchBuf, cap * sizeof(LaunchRow)));
+      pb->launchCap = cap;
+    }
+    HIPCHK(hipEventCreate(&le0));
+    HIPCHK(hipEventCreate(&le1));
+    HIPCHK(hipMemsetAsync(pb->launchBuf, 0xFF, (size_t)nc * sizeof(LaunchRow), st));
+    HIPCHK(hipEventRecord(le0, st));
+    HIPCHK(launch_lists(pb->dev, W, pb->nameRank, nc, (LaunchRow*)pb->launchBuf, st));
+    HIPCHK(hipEventRecord(le1, st));
+    dl(lrows, pb->launchBuf, (size_t)nc, st);
+  }
   dl(order, W.order, nc, st);
   dl(ctpl, W.c_tpl, nc, st);
   dl(chost, W.c_host, nc, st);
@@ -863,6 +919,7 @@ static ks_results* collect(ks_problem* pb, const KsWork& W) {
     if (logt[i] >= 0) claimPods[logt[i]].push_back(logp[i]);
     else nodePods[-logt[i] - 1].push_back(logp[i]);
   }
+  std::vector<char> launchMark(launch ? (size_t)std::max(d.T, 1) : 0, 0);
   for (int k = 0; k < nc; k++) {
     int c = order[k];
     ks_results::Claim cl;
@@ -908,7 +965,33 @@ static ks_results* collect(ks_problem* pb, const KsWork& W) {
       cl.reqQty.push_back(qty_str(kv.second));
     }
     cl.rec.assign(crs.begin() + (size_t)c * d.RSW, crs.begin() + (size_t)(c + 1) * d.RSW);
+    if (launch) {
+      // the device's row against what the replay saw: the option count, every slot of the cut written once
+      // (the 0xFF fill reads back as -1; an id stored twice leaves another slot unwritten) with one of the claim's options
+      auto fail = [&](const std::string& m) {
+        throw KsError(KS_ERR_INTERNAL, "device state check: launch list of NodeClaim " + std::to_string(k) + ": " + m);
+      };
+      const LaunchRow& row = lrows[(size_t)k];
+      const int nopt = (int)cl.its.size(), ncut = std::min(nopt, kLaunchMax);
+      if (row.n_options != nopt) fail("counts " + std::to_string(row.n_options) + " options, the replay " + std::to_string(nopt));
+      if (row.n_launch != ncut) fail("holds " + std::to_string(row.n_launch) + " entries, not " + std::to_string(ncut));
+      for (int it : cl.its) launchMark[(size_t)it] = 1;
+      for (int i = 0; i < ncut; i++) {
+        const int32_t it = row.its[i];
+        if (it < 0 || it >= d.T || launchMark[(size_t)it] != 1)
+          fail("slot " + std::to_string(i) + " holds " + std::to_string(it) + ", not an unlisted option of the claim");
+        launchMark[(size_t)it] = 2;
+        if (row.prices[i] != row.prices[i]) fail("slot " + std::to_string(i) + " has no price");
+      }
+      for (int it : cl.its) launchMark[(size_t)it] = 0;
+      cl.launchIts.assign(row.its, row.its + ncut);
+      cl.launchPrices.assign(row.prices, row.prices + ncut);
+    }
     res->claims.push_back(std::move(cl));
+  }
+  if (launch) {
+    res->hasLaunch = true;
+    if (le0) HIPCHK(hipEventElapsedTime(&res->launchMs, le0, le1));
   }
   for (auto& c : res->claims) c.bind();  // after the last move of the claims vector
   pt.mark("claims");
@@ -1212,12 +1295,8 @@ int ks_problem_check_binary(const void* buf, size_t len) {
 }
 
 // Host-only encode (no device): layout sizes for diagnostics and CPU tests.
-int ks_problem_inspect(const char* json, size_t len, char** out) {
-  API_TRY
-  if (!json || !out) throw KsError(KS_ERR_ARG, "null argument");
-  ksjson::Value root = ksjson::Parser(json, len ? len : strlen(json)).parse();
-  Host h;
-  h.build(root);
+extern "C++" {
+static std::string inspect_json(const Host& h) {
   const KsDims& d = h.dims;
   std::string o = "{";
   auto kv = [&](const char* k, long long v) { o += std::string(o.size() > 1 ? "," : "") + "\"" + k + "\":" + std::to_string(v); };
@@ -1294,6 +1373,16 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
                     bytes <= kTplTableMaxBytes;
     kv("tplClasses", ncls); kv("tplTableBytes", (long long)bytes); kv("tplTable", on ? 1 : 0);
   }
+  // launch lists: per template, the name rank (it_name_rank) of each list position; the duplicate-name refusal or ""
+  o += ",\"nameRank\":[";
+  for (int t = 0; t < d.NTPL; t++) {
+    o += t ? ",[" : "[";
+    for (int i = h.tab.tpl_it_beg[(size_t)t]; i < h.tab.tpl_it_beg[(size_t)t + 1]; i++)
+      o += (i > h.tab.tpl_it_beg[(size_t)t] ? "," : "") + std::to_string(h.tab.it_name_rank[(size_t)h.tab.tpl_its[(size_t)i]]);
+    o += "]";
+  }
+  o += "],\"launchListsRefusal\":";
+  ksjson::quote(o, launch_names_refusal(h));
   o += ",\"keyNames\":[";
   for (size_t i = 0; i < h.keyNames.size(); i++) { if (i) o += ","; ksjson::quote(o, h.keyNames[i]); }
   o += "],\"resources\":[";
@@ -1310,7 +1399,36 @@ int ks_problem_inspect(const char* json, size_t len, char** out) {
     ksjson::quote(o, h.keyNames[(size_t)__builtin_ctzll(m)]);
   }
   o += "]}";
-  *out = strdup(o.c_str());
+  return o;
+}
+}  // extern "C++"
+
+int ks_problem_inspect(const char* json, size_t len, char** out) {
+  API_TRY
+  if (!json || !out) throw KsError(KS_ERR_ARG, "null argument");
+  ksjson::Value root = ksjson::Parser(json, len ? len : strlen(json)).parse();
+  Host h;
+  h.build(root);
+  *out = strdup(inspect_json(h).c_str());
+  return KS_OK;
+  API_CATCH
+}
+
+// The same document for a binary snapshot (ks_problem_save / ks_problem_encode_binary), loaded and checked as
+// ks_problem_create_binary does it, without a device.
+int ks_problem_inspect_binary(const void* buf, size_t len, char** out) {
+  API_TRY
+  if (!buf || !out) throw KsError(KS_ERR_ARG, "null argument");
+  Host h;
+  try {
+    ArIn a{(const char*)buf, (const char*)buf + len};
+    snapshot_check_header(a, kProblemMagic);
+    host_load(a, h);
+    if (a.p != a.end) throw KsError(KS_ERR_PARSE, "binary snapshot has trailing bytes");
+  } catch (const ArchiveError& e) {
+    throw KsError(KS_ERR_PARSE, e.what());
+  }
+  *out = strdup(inspect_json(h).c_str());
   return KS_OK;
   API_CATCH
 }
@@ -1583,6 +1701,14 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
   int reps = opts && opts->replicas > 1 ? opts->replicas : 1;
   DeviceGuard guard(pb->device, opts);
   const KsDims& d = pb->host.dims;
+  const bool launchLists = opts && opts->launch_lists && !opts->timing_only;
+  if (launchLists) {  // (once per problem, when lists are first asked for)
+    if (pb->launchNames == 0) {
+      pb->launchRefusal = launch_names_refusal(pb->host);
+      pb->launchNames = pb->launchRefusal.empty() ? 1 : -1;
+    }
+    if (pb->launchNames < 0) throw KsError(KS_ERR_UNSUPPORTED, pb->launchRefusal);
+  }
   // one Solve per CU gets the whole 160 KiB; larger batches trade LDS for waves per CU
   size_t budget = 160 * 1024 - 256;
   if (reps > 256) budget = std::max<size_t>(24 * 1024, budget * 256 / reps);
@@ -1690,7 +1816,7 @@ int ks_solve(ks_problem* pb, const ks_solve_opts* opts, ks_results** out) {
     }
     r->algbytes = (double)r->counters[CT_ALGBYTES];
   } else {
-    r = collect(pb, w0);
+    r = collect(pb, w0, launchLists);
   }
   r->routes = routes;
   r->plan = pl;
@@ -1802,6 +1928,17 @@ int ks_results_nodeclaim_requirements(const ks_results* r, int i, int* n, const 
   if (reqs) *reqs = c.reqC.data();
   return KS_OK;
 }
+int ks_results_nodeclaim_launch(const ks_results* r, int i, const int32_t** instance_types, const double** prices, int* n,
+                                int* n_options) {
+  if (!r || !r->hasLaunch || i < 0 || i >= (int)r->claims.size()) return KS_ERR_ARG;
+  const auto& c = r->claims[(size_t)i];
+  if (instance_types) *instance_types = c.launchIts.data();
+  if (prices) *prices = c.launchPrices.data();
+  if (n) *n = (int)c.launchIts.size();
+  if (n_options) *n_options = (int)c.its.size();
+  return KS_OK;
+}
+double ks_results_launch_ms(const ks_results* r) { return r ? r->launchMs : 0; }
 int ks_results_num_existing_nodes(const ks_results* r) { return (int)r->nodes.size(); }
 int ks_results_existing_node(const ks_results* r, int i, int* idx, const int32_t** pods, int* np) {
   if (i < 0 || i >= (int)r->nodes.size()) return KS_ERR_ARG;

@@ -866,6 +866,16 @@ void Host::build(const Value& root) {
     }
     tab.it_off_beg[i + 1] = (int)tab.off_zone.size();
   }
+  {
+    std::vector<int32_t> byName((size_t)T);
+    for (int i = 0; i < T; i++) byName[(size_t)i] = i;
+    std::sort(byName.begin(), byName.end(), [&](int32_t a, int32_t b) {
+      const int c = its[(size_t)a].name.compare(its[(size_t)b].name);  // (char_traits<char>: bytes as unsigned)
+      return c != 0 ? c < 0 : a < b;
+    });
+    tab.it_name_rank.assign((size_t)std::max(T, 1), 0);
+    for (int r = 0; r < T; r++) tab.it_name_rank[(size_t)byName[(size_t)r]] = r;
+  }
   itKeys |= (1ull << zoneKey) | (1ull << ctKey);
   if (tab.off_zone.empty()) { tab.off_zone.push_back(0); tab.off_ct.push_back(0); tab.off_price.push_back(0); }
 

@@ -218,6 +218,9 @@ struct Host {
     std::vector<uint32_t> fk_words;
     std::vector<int32_t> fk_key_off;  // [NTPL][NK] block of key k in template t, -1: no table
     std::vector<int32_t> fk_tpl;      // [NTPL][3]: all positions, irregular positions, offerings
+    // [T] rank of the instance type's name in bytewise string order (equal names: by index): OrderByPrice's
+    // tie-break (types.go:70-75), read by k_launch_lists
+    std::vector<int32_t> it_name_rank;
   } tab;
 
   void build(const ksjson::Value& root);

@@ -132,6 +132,12 @@ struct ks_problem {
   size_t tplBlock = 0;         // byte offset of the fresh-NodeClaim block in dbuf when it holds classes and a table
   int tplTableState = 0;       // 0 not decided yet, 1 built, -1 none (see build_tpl_table)
   float tplTableMs = 0;        // k_fresh_claims by events, when it was built
+  // Launch lists (ks_launch.hip; ks_solve_opts.launch_lists)
+  const int32_t* nameRank = nullptr;  // Host::Tables::it_name_rank in dbuf
+  void* launchBuf = nullptr;          // the rows of the last Solve that asked for them, launchCap rows allocated
+  size_t launchCap = 0;
+  int launchNames = 0;                // 0 not checked yet, 1 the templates' names are unique, -1 refused (launchRefusal)
+  std::string launchRefusal;
   ~ks_problem() {
     int prev = -1;
     if (device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device) (void)hipSetDevice(device);
@@ -142,6 +148,7 @@ struct ks_problem {
     if (dbuf) (void)hipFree(dbuf);
     if (fmbuf) (void)hipFree(fmbuf);
     if (fnbuf) (void)hipFree(fnbuf);
+    if (launchBuf) (void)hipFree(launchBuf);
     if (wbuf) (void)hipFree(wbuf);
     if (works_dev) (void)hipFree(works_dev);
     if (stream) (void)hipStreamDestroy(stream);

@@ -78,7 +78,7 @@ template <class A> void io_tables(A& a, Host::Tables& t, uint64_t rsw) {
          t.pod_vs, t.pod_vubeg, t.pod_vu, t.vol_udrv, t.n_vc0, t.n_vlim, t.tg_meta, t.tg_cnt0, t.tg_frs, t.st_gown, t.pod_gsel, t.pod_ginv, t.n_tdom, t.it_rs, t.tpl_rs, t.n_rs0,
          t.pool_mask, t.st_toltpl, t.tpl_taint, t.st_tol, t.n_taint, t.tsort_pos, t.it_off_beg, t.off_zone, t.off_ct,
          t.tpl_it_beg, t.tpl_its, t.tpl_pool, t.pod_state0, t.pod_nstate, t.pod_uid, t.st_flags, t.pod_rmask, t.tpl_rmask,
-         t.pod_rfmt, t.tpl_rfmt, t.fk_words, t.fk_key_off, t.fk_tpl, t.tg_late);
+         t.pod_rfmt, t.tpl_rfmt, t.fk_words, t.fk_key_off, t.fk_tpl, t.tg_late, t.it_name_rank);
   // (st_rss is one word when the problem has no topology groups)
   io_rows(a, t.st_rs, rsw);
   io_rows(a, t.st_rss, t.st_rss.size() < rsw && !A::reading ? t.st_rss.size() : rsw);
@@ -162,6 +162,9 @@ void host_check(const Host& h) {
   need(t.it_cap.size(), T * R, "it_cap");
   need(t.it_rs.size(), T * RSW, "it_rs");
   need(t.it_off_beg.size(), T + 1, "it_off_beg");
+  need(t.it_name_rank.size(), std::max<int64_t>(T, 1), "it_name_rank");
+  for (int64_t i = 0; i < T; i++)
+    if (t.it_name_rank[(size_t)i] < 0 || t.it_name_rank[(size_t)i] >= T) bad("instance-type name rank");
   need(t.tpl_rs.size(), NT1 * RSW, "tpl_rs");
   need(t.tpl_taint.size(), NT1 * 2, "tpl_taint");
   need(t.tpl_daemon.size(), NT1 * R, "tpl_daemon");
@@ -317,13 +320,13 @@ template <class A> void host_io(A& a, Host& h) {
 // Layout guards: adding a member to one of these types changes its size and stops the build here until the
 // member is listed above (sizes of this toolchain's libstdc++, x86-64).
 static_assert(sizeof(PodH) == 640, "PodH changed: update io(PodH) in ks_snapshot.cpp");
-static_assert(sizeof(Host::Tables) == 1464, "Host::Tables changed: update io(Host::Tables)");
+static_assert(sizeof(Host::Tables) == 1488, "Host::Tables changed: update io(Host::Tables)");
 static_assert(sizeof(Host::Node) == 456, "Host::Node changed: update io(Host::Node)");
 static_assert(sizeof(Host::Tpl) == 280, "Host::Tpl changed: update io(Host::Tpl)");
 static_assert(sizeof(Host::IT) == 224, "Host::IT changed: update io(Host::IT)");
 static_assert(sizeof(TopoGroup) == 256, "TopoGroup changed: update io(TopoGroup)");
 static_assert(sizeof(PodState) == 144, "PodState changed: update io(PodState)");
-static_assert(sizeof(Host) == 3000, "Host changed: update host_io");
+static_assert(sizeof(Host) == 3024, "Host changed: update host_io");
 static_assert(sizeof(HostPortH) == 88 && sizeof(AffTerm) == 128 && sizeof(SpreadC) == 104 && sizeof(LabelSel) == 32,
               "a pod-spec type changed: update its io()");
 

@@ -33,7 +33,7 @@ class KsError(RuntimeError):
 class _Opts(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int), ("simulation_mode", ctypes.c_int), ("replicas", ctypes.c_int),
                 ("timing_only", ctypes.c_int), ("lds_budget", ctypes.c_int),
-                ("reserved", ctypes.c_int * 3)]
+                ("launch_lists", ctypes.c_int), ("reserved", ctypes.c_int * 2)]
 
 
 class _Clock(ctypes.Structure):  # ks_cons_clock
@@ -56,6 +56,7 @@ def lib():
     vp = ctypes.c_void_p
     l.ks_problem_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp)]
     l.ks_problem_inspect.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp)]
+    l.ks_problem_inspect_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp)]
     l.ks_problem_free.argtypes = [vp]
     l.ks_solve.argtypes = [vp, ctypes.POINTER(_Opts), ctypes.POINTER(vp)]
     l.ks_results_free.argtypes = [vp]
@@ -110,6 +111,14 @@ def _take_str(ptr):
 
 def _encode(snapshot):
     return (snapshot if isinstance(snapshot, str) else json.dumps(snapshot)).encode()
+
+
+def inspect_binary(blob):
+    """inspect() of a binary snapshot (save() / encode_binary()), loaded as from_binary() loads it; no device."""
+    blob = bytes(blob)
+    out = ctypes.c_void_p()
+    _check(lib().ks_problem_inspect_binary(blob, len(blob), ctypes.byref(out)))
+    return json.loads(_take_str(out))
 
 
 def _records_buffer(records):
@@ -300,6 +309,9 @@ def _bind_accessors(l):
     l.ks_results_existing_node.argtypes = [vp, ctypes.c_int, ip, i32pp, ip]
     l.ks_results_num_pod_errors.argtypes = [vp]
     l.ks_results_pod_error.argtypes = [vp, ctypes.c_int, ip, ctypes.POINTER(ctypes.c_char_p)]
+    l.ks_results_nodeclaim_launch.argtypes = [vp, ctypes.c_int, i32pp, ctypes.POINTER(ctypes.POINTER(ctypes.c_double)), ip, ip]
+    l.ks_results_launch_ms.argtypes = [vp]
+    l.ks_results_launch_ms.restype = ctypes.c_double
     _accessors_bound = True
 
 
@@ -307,17 +319,22 @@ class StructuredResults:
     """Results read through the C-ABI's structured accessors (what the cgo shim in INTEGRATION.md does):
     new_nodeclaims = [{template, pods, instance_types (indices), requests {name: quantity},
     requirements [(key, op, values, gt, lt)]}], existing_nodes = [(state node index, pods)],
-    pod_errors = {pod index: message}."""
+    pod_errors = {pod index: message}.  After solve_structured(launch_lists=True) every claim also carries
+    launch (instance-type names in OrderByPrice order, the first 100), launch_prices (the price that ordered each)
+    and n_options, and launch_ms is the launch-list kernel's time; otherwise the claims have no such keys and
+    launch_ms is 0."""
 
-    def __init__(self, claims, nodes, errors, kernel_ms, solve_kernel_ms):
+    def __init__(self, claims, nodes, errors, kernel_ms, solve_kernel_ms, launch_ms=0.0):
         self.new_nodeclaims = claims
         self.existing_nodes = nodes
         self.pod_errors = errors
         self.kernel_ms = kernel_ms
         self.solve_kernel_ms = solve_kernel_ms
+        self.launch_ms = launch_ms
 
 
-def _read_structured(l, r):
+def _read_structured(l, r, launch_names=None):
+    """launch_names: the snapshot's instance-type names when the Solve set launch_lists (None: no launch data)."""
     import numpy as np
 
     _bind_accessors(l)
@@ -341,6 +358,12 @@ def _read_structured(l, r):
                          x.gt if x.has_gt else None, x.lt if x.has_lt else None))
         claims.append({"template": tpl.value, "pods": pods, "instance_types": its, "requests": requests,
                        "requirements": reqs})
+        if launch_names is not None:
+            pr = ctypes.POINTER(ctypes.c_double)()
+            _check(l.ks_results_nodeclaim_launch(r, i, ctypes.byref(a1), ctypes.byref(pr), ctypes.byref(n1), ctypes.byref(n2)))
+            claims[-1]["launch"] = [launch_names[a1[k]] for k in range(n1.value)]
+            claims[-1]["launch_prices"] = [pr[k] for k in range(n1.value)]
+            claims[-1]["n_options"] = n2.value
     nodes = []
     for i in range(l.ks_results_num_existing_nodes(r)):
         _check(l.ks_results_existing_node(r, i, ctypes.byref(n2), ctypes.byref(a1), ctypes.byref(n1)))
@@ -445,6 +468,8 @@ class Scheduler:
 
     def __init__(self, snapshot, _binary=None, _host_only=False):
         h = ctypes.c_void_p()
+        # launch lists are reported by name: the names are read from the snapshot on first use (a reference, no copy)
+        self._snapshot, self._it_names = snapshot, None
         if _host_only:
             b = _encode(snapshot)
             lib().ks_problem_create_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
@@ -570,16 +595,34 @@ class Scheduler:
         finally:
             lib().ks_results_free(r)
 
-    def solve_structured(self, device=-1, simulation_mode=True):
+    def _instance_type_names(self):
+        if self._it_names is None:
+            if self._snapshot is None:
+                raise KsError(-6, "launch lists by name need the JSON snapshot the Scheduler was created from")
+            doc = self._snapshot if isinstance(self._snapshot, dict) else json.loads(self._snapshot)
+            self._it_names = [it["name"] for it in doc.get("instanceTypes", [])]
+            self._snapshot = None
+        return self._it_names
+
+    def solve_structured(self, device=-1, simulation_mode=True, launch_lists=False, lds_budget=0, with_json=False):
         """Solve(ctx, pods) with the Results read through the structured accessors (no JSON): the drop-in
-        caller's full return path (INTEGRATION.md's cgo shim)."""
+        caller's full return path (INTEGRATION.md's cgo shim).  launch_lists: every claim also carries its launch
+        list (ks_results_nodeclaim_launch), computed on the device.  with_json: the same Results' ks_results_json
+        document as .doc (tests compare the two)."""
         l = lib()
-        o = _Opts(device, 1 if simulation_mode else 0, 1, 0, 0)
+        names = self._instance_type_names() if launch_lists else None
+        o = _Opts(device, 1 if simulation_mode else 0, 1, 0, lds_budget, 1 if launch_lists else 0)
         r = ctypes.c_void_p()
         _check(l.ks_solve(self._h, ctypes.byref(o), ctypes.byref(r)))
         try:
-            claims, nodes, errors = _read_structured(l, r)
-            return StructuredResults(claims, nodes, errors, l.ks_results_kernel_ms(r), l.ks_results_solve_kernel_ms(r))
+            claims, nodes, errors = _read_structured(l, r, names)
+            out = StructuredResults(claims, nodes, errors, l.ks_results_kernel_ms(r), l.ks_results_solve_kernel_ms(r),
+                                    l.ks_results_launch_ms(r))
+            if with_json:
+                js = ctypes.c_void_p()
+                _check(l.ks_results_json(r, ctypes.byref(js)))
+                out.doc = json.loads(_take_str(js))
+            return out
         finally:
             l.ks_results_free(r)
 
