@@ -44,7 +44,10 @@ typedef struct ks_solve_opts {
                           HBM-resident claim path) */
   int launch_lists;    /* 1: also compute every NewNodeClaim's launch list on the device
                           (ks_results_nodeclaim_launch); 0: no launch data, Results as without the field.
-                          Ignored with timing_only */
+                          Ignored with timing_only.  ks_cons_run / ks_cons_disrupt: also compute the
+                          launch list of every replacement (ks_cons_claim_launch,
+                          ks_cons_disrupt_launch); 0: nothing is computed and every document is as
+                          without the field */
   int reserved[2];
 } ks_solve_opts;
 
@@ -363,6 +366,30 @@ int ks_cons_needed_sims(ks_cons* c, const void* records, int world, int flags, i
 int ks_cons_claim_requirements(ks_cons* c, int sim, uint32_t* out);
 int ks_cons_decide(ks_cons* c, const void* records, int world, int flags, const uint32_t* rs_table,
                    char** json_out);
+/* Launch lists of a pass (ks_cons_run with opts->launch_lists set): behind the simulations, one more kernel orders
+ * the options of every simulation whose action is replace the way NodeClaimTemplate.ToNodeClaim launches the
+ * replacement (see ks_results_nodeclaim_launch): the command's instanceTypeOptions (after filterByPrice; after
+ * filterOutSameType for a multi-node prefix) priced under NewNodeClaims[0]'s requirements, narrowed to spot where
+ * the command's are (consolidation.go:181-188), by (price, name), cut to 100.  The rows stay on the GPU that ran
+ * the simulation.  kernel_ms does not include that kernel; ks_cons_launch_ms is its HIP-event time.  The run
+ * fails with KS_ERR_UNSUPPORTED / KS_ERR_CAPACITY as a Solve with launch_lists does (a template listing one name
+ * twice; a list too long for the LDS).
+ * ks_cons_claim_launch: simulation `sim`'s list, read on its owner (rank = sim % world) and checked on the host
+ * against the command's option words first (a failed check is KS_ERR_INTERNAL).  instance_types / prices: room for
+ * 100 entries; *n = min(*n_options, 100); any out pointer may be NULL.  KS_ERR_ARG when the simulation is not in
+ * this handle's last run, when that run did not set launch_lists, and when the simulation's action is not replace.
+ * ks_cons_decide / ks_cons_decide_clock after such a run: every replace command gains "sim" (the simulation to ask,
+ * -1 for a carried probe), and its "replacement" gains "launchInstanceTypes": [names] and "launchPrices": [numbers]
+ * when the list is in this handle: at world 1 with rs_table NULL, and at any world for a command chosen from a
+ * carried probe (its re-run is local and computes its list with the same kernel). */
+int ks_cons_claim_launch(ks_cons* c, int sim, int32_t* instance_types, double* prices, int* n, int* n_options);
+/* HIP-event time (milliseconds) of the launch-list kernel of the handle's last ks_cons_run or ks_cons_disrupt; 0
+ * when that call did not set launch_lists or its command has no replacement to order (no simulation; no pick). */
+double ks_cons_launch_ms(const ks_cons* c);
+/* The name of instance type `instance_type` as the launch lists index it (the handle's instanceTypes order, also
+ * after a binary load); lives as long as the handle.  NULL out of range and for a handle a failed update left
+ * unusable. */
+const char* ks_cons_instance_type_name(const ks_cons* c, int instance_type);
 /* The methods' timeouts (MultiNodeConsolidationTimeoutDuration = 1 min, multinodeconsolidation.go:34,99-110;
  * SingleNodeConsolidationTimeoutDuration = 3 min, singlenodeconsolidation.go:29,58-65) on a virtual clock
  * that advances sim_seconds per simulation the sequential replay consults: the multi-node search returns
@@ -413,7 +440,15 @@ int ks_cons_validate(ks_cons* c, const char* command_json, size_t len, const ks_
  * some pods naming it while its sum is zero). */
 #define KS_DISRUPT_EXPIRATION 1
 #define KS_DISRUPT_DRIFT 2
+/* With opts->launch_lists set every entry of "replacements" also carries "launchInstanceTypes" / "launchPrices":
+ * its launch list, computed by a kernel enqueued behind the pick (no host round trip between them) and checked on
+ * the host.  The refusals are ks_cons_run's.  The all-empty and no-pick commands have no replacement. */
 int ks_cons_disrupt(ks_cons* c, int method, const ks_solve_opts* opts, int flags, char** json_out);
+/* Replacement i of the handle's last ks_cons_disrupt, as ks_results_nodeclaim_launch hands out a Solve's: the
+ * arrays live until the handle's next ks_cons_disrupt.  KS_ERR_ARG for i out of range and when that call did not
+ * set launch_lists. */
+int ks_cons_disrupt_launch(const ks_cons* c, int i, const int32_t** instance_types, const double** prices, int* n,
+                           int* n_options);
 /* Host-only, no device: {"method", "candidates": [names in the method's order], "empty": [the empty ones],
  * "transitionTimes": [seconds]} of the snapshot with update_json applied (NULL or "{}": none; an array: a sequence). */
 int ks_cons_inspect_disrupt(const char* snapshot_json, size_t len, const char* update_json, size_t ulen, int method,

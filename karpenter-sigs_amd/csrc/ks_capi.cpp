@@ -803,7 +803,7 @@ static KsError claim_cap_error(const ks_problem* pb) {
 // Launch lists need a total order: (price, name) is one only when no template lists two instance types of the
 // same name (Go's sort.Slice is not stable, so equal keys have no defined order).  "" when every template's names
 // are unique, else the refusal naming the first template and name.
-static std::string launch_names_refusal(const Host& h) {
+std::string launch_names_refusal(const Host& h) {
   for (size_t t = 0; t < h.tpls.size(); t++) {
     std::vector<int> ids(h.tpls[t].its.begin(), h.tpls[t].its.end());
     std::sort(ids.begin(), ids.end(), [&](int a, int b) { return h.its[(size_t)a].name < h.its[(size_t)b].name; });
@@ -814,6 +814,18 @@ static std::string launch_names_refusal(const Host& h) {
                "; OrderByPrice has no defined order for them";
   }
   return "";
+}
+
+void require_launch_lists(ks_problem* pb) {
+  if (pb->launchNames == 0) {
+    pb->launchRefusal = launch_names_refusal(pb->host);
+    pb->launchNames = pb->launchRefusal.empty() ? 1 : -1;
+  }
+  if (pb->launchNames < 0) throw KsError(KS_ERR_UNSUPPORTED, pb->launchRefusal);
+  const KsDims& d = pb->host.dims;
+  if (launch_lds_bytes(d.TW, d.RSW) > kLaunchMaxLds)
+    throw KsError(KS_ERR_CAPACITY, "launch lists: a template's instance-type list (" + std::to_string(d.maxTplIts) +
+                                       ") is too long for the kernel's LDS");
 }
 
 // Rebuild Results from the replica-0 workspace.  launch: also every claim's launch list (k_launch_lists).

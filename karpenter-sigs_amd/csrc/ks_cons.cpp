@@ -36,6 +36,7 @@
 #include "ks_archive.h"
 #include "ks_disrupt.h"
 #include "ks_host.h"
+#include "ks_launch.h"
 #include "ks_parallel.h"
 #include "ks_runtime.h"
 
@@ -303,9 +304,15 @@ struct ks_cons {
     size_t capTopoB = 0, capHtopoB = 0, capHworksB = 0;
     // allocation capacities: a new plan (another rank / world, an update) reuses the buffers that fit
     size_t capBuf = 0, capWorks = 0, capRec = 0, capHrec = 0, capEnt = 0, capRunw = 0, capTemp = 0, capHdr = 0, capHhdr = 0;
+    // Launch lists (ks_solve_opts.launch_lists): one row per launch slot, k_launch_lists_sims' output; they stay on
+    // this GPU like the requirement records.  listed: the last launch of this plan filled them.
+    LaunchRow* lrows = nullptr;
+    size_t capRows = 0;
+    bool listed = false;
     void release() {
       for (void* p : {(void*)lbuf, (void*)lworks, (void*)lrec, (void*)lentries, (void*)lentrySim, (void*)lpodmap,
-                      (void*)lrunlen, (void*)lrunw, (void*)lkeys, (void*)lvals, ltemp, (void*)lhdr, (void*)lst, ltopoB})
+                      (void*)lrunlen, (void*)lrunw, (void*)lkeys, (void*)lvals, ltemp, (void*)lhdr, (void*)lst, ltopoB,
+                      (void*)lrows})
         if (p) (void)hipFree(p);
       if (hrec) (void)hipHostFree(hrec);
       if (hhdr) (void)hipHostFree(hhdr);
@@ -321,6 +328,7 @@ struct ks_cons {
       lnent = lrbits = lsbits = lnmw = 0;
       lsorted = false;
       hdrOnly = keptFull = false;
+      listed = false;
       lplan = Plan{};
       pipeB = false;
       nA = 0;
@@ -344,6 +352,7 @@ struct ks_cons {
     int sim = -1;               // the pass's simulation of the prefix
     std::vector<int32_t> rec;   // carried: the re-run's record
     std::vector<uint32_t> rs;   // carried: its NewNodeClaims[0] requirements (when it has a NodeClaim)
+    std::vector<LaunchRow> launch;  // carried, a Replace, the pass set launch_lists: its launch list (one row)
   };
   struct Walk {
     bool valid = false;
@@ -375,6 +384,24 @@ struct ks_cons {
   // the k_solve launches since the last ks_cons_run began, in order: the pass's (both streams of a split or a
   // two-phase topology plan), then those of the carried-probe re-runs and of validate() (ks_cons_last_routes)
   std::vector<Route> routes;
+  // Launch lists: the timing events of the launch-list kernels, the time of the last pass's / method's kernel, and
+  // whether the last ks_cons_run set ks_solve_opts.launch_lists
+  hipEvent_t evL[2] = {nullptr, nullptr};
+  float launchMs = 0;
+  bool passLists = false;
+  // ... of the last ks_cons_disrupt: the rows of the pick's NodeClaims (device, pinned host; ldMaxP rows, the
+  // plan's bound on NodeClaims) and the checked lists ks_cons_disrupt_launch hands out
+  LaunchRow* drows = nullptr;
+  LaunchRow* hrows = nullptr;
+  size_t capDrows = 0;
+  int ldMaxP = 0;
+  bool dlValid = false;
+  struct DisruptList {
+    int nopt = 0;
+    std::vector<int32_t> its;
+    std::vector<double> prices;
+  };
+  std::vector<DisruptList> dl;
 
   int sim_of_multi(int mid) const { return multiHi - mid; }  // mid in [1, multiHi]
   int sim_of_single(int i) const { return multiHi + i; }
@@ -393,6 +420,10 @@ struct ks_cons {
     if (dout) (void)hipFree(dout);
     if (dpos) (void)hipFree(dpos);
     if (hout) (void)hipHostFree(hout);
+    if (drows) (void)hipFree(drows);
+    if (hrows) (void)hipHostFree(hrows);
+    for (hipEvent_t e : evL)
+      if (e) (void)hipEventDestroy(e);
     if (rank) (void)hipFree(rank);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -1420,10 +1451,47 @@ std::vector<int> bits_to_its(const Host& h, int tpl, const int32_t* bits) {
   return out;
 }
 
+// A launch-list row against the option words it was computed from, before it is handed out (as collect() checks a
+// Solve's rows): the option count, the cut, every slot of the cut written once (the 0xFF fill reads back as -1; an
+// id stored twice leaves another slot unwritten) with one of the options and a price, and the order itself: the
+// key (price, name rank) rises from slot to slot (prices compare as Go's float64 do, so -0.0 ties with +0.0).
+void check_launch_row(const Host& h, int tpl, const int32_t* bits, const LaunchRow& row, const std::string& what) {
+  auto fail = [&](const std::string& m) { throw KsError(KS_ERR_INTERNAL, "launch list of " + what + ": " + m); };
+  if (tpl < 0 || tpl >= h.dims.NTPL) fail("template out of range");
+  const std::vector<int> its = bits_to_its(h, tpl, bits);
+  const int nopt = (int)its.size(), ncut = std::min(nopt, kLaunchMax);
+  if (row.n_options != nopt) fail("counts " + std::to_string(row.n_options) + " options, the command " + std::to_string(nopt));
+  if (row.n_launch != ncut) fail("holds " + std::to_string(row.n_launch) + " entries, not " + std::to_string(ncut));
+  std::set<int> left(its.begin(), its.end());
+  for (int i = 0; i < ncut; i++) {
+    if (!left.erase(row.its[i]))
+      fail("slot " + std::to_string(i) + " holds " + std::to_string(row.its[i]) + ", not an unlisted option of the command");
+    if (row.prices[i] != row.prices[i]) fail("slot " + std::to_string(i) + " has no price");
+    if (i > 0) {
+      const double a = row.prices[i - 1], b = row.prices[i];
+      const int32_t ra = h.tab.it_name_rank[(size_t)row.its[i - 1]], rb = h.tab.it_name_rank[(size_t)row.its[i]];
+      if (a > b || (a == b && ra >= rb)) fail("slot " + std::to_string(i) + " is out of OrderByPrice order");
+    }
+  }
+}
+
+// ,"launchInstanceTypes":[names],"launchPrices":[%.17g] of a checked row
+std::string launch_fields_json(const Host& h, const int32_t* its, const double* prices, int n) {
+  std::string o = ",\"launchInstanceTypes\":" + names_json(h, std::vector<int>(its, its + n)) + ",\"launchPrices\":[";
+  char buf[40];
+  for (int i = 0; i < n; i++) {
+    snprintf(buf, sizeof buf, "%s%.17g", i ? "," : "", prices[i]);
+    o += buf;
+  }
+  return o + "]";
+}
+
 // The reference's sequential selection over the simulation records.
 // rsOf(sim): NewNodeClaims[0]'s requirement record of simulation `sim` (kept in the workspace of the
 // GPU that ran it; ks_cons_needed_sims lists the simulations whose record the output needs).
 using RsFn = std::function<const uint32_t*(int)>;
+// launchOf(sim): the launch-list row of the pass's simulation `sim` when this handle holds it, else null.
+using LaunchFn = std::function<const LaunchRow*(int)>;
 // clk: the methods' timeouts on a virtual clock that advances clk->sim_seconds per simulation the replay
 // consults (MultiNodeConsolidation's 1 min, multinodeconsolidation.go:34,99-110; SingleNodeConsolidation's
 // 3 min, singlenodeconsolidation.go:29,58-65); null or sim_seconds 0: the clock never passes a timeout.
@@ -1538,7 +1606,10 @@ void rerun_probe(ks_cons& c, int mid, const std::vector<int32_t>* start, ks_cons
                  std::vector<int32_t>& podmap, std::vector<int32_t>& state);
 
 std::string decide_json(const ks_cons& c, const RecView& rv, int world, bool allSims, const RsFn& rsOf,
-                        bool withCandidates = true, const ks_cons_clock* clk = nullptr, bool withSims = true) {
+                        bool withCandidates = true, const ks_cons_clock* clk = nullptr, bool withSims = true,
+                        const LaunchFn* launchOf = nullptr) {
+  // launchOf set: the pass ran with launch_lists.  Every Replace command names its simulation ("sim", -1 for a
+  // carried probe) and carries its launch list when the row is on this handle (a world-1 pass, or a carried probe)
   const double simS = clk ? clk->sim_seconds : 0.0;
   const Host& h = c.pb->host;
   const KsDims& d = h.dims;
@@ -1617,7 +1688,17 @@ std::string decide_json(const ks_cons& c, const RecView& rv, int world, bool all
       }
       o += ",\"replacement\":{\"nodePoolName\":";
       ksjson::quote(o, h.tpls[(size_t)r[RF_TPL]].pool);
-      o += ",\"instanceTypeOptions\":" + names_json(h, bits_to_its(h, r[RF_TPL], fullOf(sim) + RF_HDR + (multi ? 2 : 1) * d.TW));
+      const int32_t* optBits = fullOf(sim) + RF_HDR + (multi ? 2 : 1) * d.TW;
+      o += ",\"instanceTypeOptions\":" + names_json(h, bits_to_its(h, r[RF_TPL], optBits));
+      if (launchOf) {
+        const ks_cons::Probe* pr = sim < 0 ? &wk.probes[(size_t)(-2 - sim)] : nullptr;
+        const LaunchRow* row = pr ? (pr->launch.empty() ? nullptr : pr->launch.data()) : (*launchOf)(sim);
+        if (row) {
+          check_launch_row(h, r[RF_TPL], optBits, *row,
+                           pr ? "carried probe " + std::to_string(pr->mid) : "simulation " + std::to_string(sim));
+          o += launch_fields_json(h, row->its, row->prices, row->n_launch);
+        }
+      }
       o += ",\"requirements\":[";
       const uint64_t pr = rs_present(rs.data());
       bool first = true;
@@ -1628,6 +1709,7 @@ std::string decide_json(const ks_cons& c, const RecView& rv, int world, bool all
         ksjson::quote(o, h.reqString(rs.data(), k, true, before.at(sim) + r[RF_HOST]));
       }
       o += "]}";
+      if (launchOf) o += ",\"sim\":" + std::to_string(sim >= 0 ? sim : -1);
     }
     if (err) o += ",\"error\":true";
     return o + "}";
@@ -1698,12 +1780,21 @@ std::string decide_json(const ks_cons& c, const RecView& rv, int world, bool all
 
 namespace {
 
+// The launch-list kernels' timing events, created once per handle.
+void launch_events(ks_cons& c) {
+  if (c.evL[0]) return;
+  HIPCHK(hipEventCreate(&c.evL[0]));
+  HIPCHK(hipEventCreate(&c.evL[1]));
+}
+
 // The queue sort + simulation kernel over this rank's simulations; records to host or device memory.
 // Returns the HIP-event time of both launches on the stream they ran on.
 // tail: enqueued on the stream behind the simulations in place of the record copies (the records and
 // workspaces stay on the device for it), before the one synchronisation.
+// lists: k_launch_lists_sims over the launch's slots behind the simulations (Launch::lrows); its event time goes to
+// *listsMs.  The returned time does not include it.
 double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice,
-                const std::function<void(hipStream_t)>* tail = nullptr) {
+                const std::function<void(hipStream_t)>* tail = nullptr, bool lists = false, float* listsMs = nullptr) {
   PhaseTimer pt("run_sims");
   RouteScope routeScope(&c.routes);
   prepare_launch(c, rank, world);
@@ -1757,6 +1848,24 @@ double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice,
   }
   HIPCHK(hipEventRecord(c.ev[1], pb.stream));
   pt.mark("launches enqueued");
+  c.L.listed = false;
+  if (lists && ns > 0) {
+    // pb.stream is behind every stream the pass used: a two-phase topology plan and a split launch both make it
+    // wait on their join event (c.evJoin) above, before c.ev[1]
+    if ((size_t)ns > c.L.capRows || !c.L.lrows) {  // (sized by the plan: a later pass of this plan reuses it)
+      if (c.L.lrows) HIPCHK(hipFree(c.L.lrows));
+      c.L.lrows = nullptr;
+      c.L.capRows = 0;
+      HIPCHK(hipMalloc((void**)&c.L.lrows, (size_t)ns * sizeof(LaunchRow)));
+      c.L.capRows = (size_t)ns;
+    }
+    launch_events(c);
+    HIPCHK(hipMemsetAsync(c.L.lrows, 0xFF, (size_t)ns * sizeof(LaunchRow), pb.stream));
+    HIPCHK(hipEventRecord(c.evL[0], pb.stream));
+    HIPCHK(launch_lists_sims(pb.dev, c.L.lworks, c.L.lrec, c.recWords, pb.nameRank, ns, c.L.lrows, pb.stream));
+    HIPCHK(hipEventRecord(c.evL[1], pb.stream));
+    pt.mark("launch lists enqueued");
+  }
   // the records follow on the same stream; one synchronisation covers both
   const size_t bytes = 4 * (size_t)c.recWords * ns, all = 4 * (size_t)c.recWords * c.per_rank(world);
   if (tail) {
@@ -1789,6 +1898,10 @@ double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice,
   c.L.keptFull = !tail && !onDevice && !records && world == 1 && !c.L.hdrOnly;
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+  if (lists && ns > 0) {
+    c.L.listed = true;
+    if (listsMs) HIPCHK(hipEventElapsedTime(listsMs, c.evL[0], c.evL[1]));
+  }
   if (!onDevice && records) {  // (records == NULL: they stay in the handle's pinned buffer, host_records)
     memcpy(records, c.L.hrec, bytes);
     if (all > bytes) memset((char*)records + bytes, 0, all - bytes);
@@ -1799,6 +1912,8 @@ double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice,
 void rerun_probe(ks_cons& c, int mid, const std::vector<int32_t>* start, ks_cons::Probe& out,
                  std::vector<int32_t>& podmap, std::vector<int32_t>& state) {
   PhaseTimer pt("rerun_probe");
+  // a carried probe of a pass that set launch_lists: its launch list from the same kernel, behind the re-run
+  const bool lists = start && c.passLists;
   std::vector<ks_cons::Sim> one(1);
   one[0].multi = true;
   one[0].cands.resize((size_t)mid + 1);
@@ -1815,8 +1930,13 @@ void rerun_probe(ks_cons& c, int mid, const std::vector<int32_t>* start, ks_cons
   };
   try {
     out.rec.assign((size_t)c.recWords, 0);
-    (void)run_sims(c, 0, 1, out.rec.data(), false);
+    (void)run_sims(c, 0, 1, out.rec.data(), false, nullptr, lists);
     check_record(c.pb->host, out.rec.data(), "multi-node probe " + std::to_string(mid) + " (carried)");
+    out.launch.clear();
+    if (lists && c.L.listed && out.rec[RF_ACTION] == CA_REPLACE) {
+      out.launch.resize(1);
+      HIPCHK(hipMemcpy(out.launch.data(), c.L.lrows, sizeof(LaunchRow), hipMemcpyDeviceToHost));
+    }
     const KsWork& w = c.L.lhost[0];
     const int RSW = c.pb->host.dims.RSW;
     out.rs.clear();
@@ -2721,6 +2841,12 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
   }
   const std::vector<int>& order = c.ldOrder;
   const int n = (int)order.size();
+  // launch lists (opts->launch_lists): every replacement's, from k_launch_lists_export behind the pick
+  const bool lists = opts && opts->launch_lists;
+  c.dlValid = false;
+  c.dl.clear();
+  c.launchMs = 0;
+  if (lists) require_launch_lists(c.pb.get());
   std::string o = std::string("{\"method\":\"") + method_name(method) + "\",\"candidates\":";
   put_names(o, c, order, false);
   bool anyEmpty = false;
@@ -2730,6 +2856,7 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
     o += std::string(",\"command\":{\"action\":\"") + (anyEmpty ? "delete" : "no-op") + "\",\"candidates\":";
     if (anyEmpty) put_names(o, c, order, true);
     else o += "[]";
+    c.dlValid = lists;  // (no replacement, nothing launched)
     return o + ",\"replacements\":[]},\"sims\":[],\"kernel_ms\":0}";
   }
   // the method's plan: one single-candidate simulation per candidate, in the method's order, in a launch of its
@@ -2753,6 +2880,7 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
     }
     // a simulation of P pods creates at most P claims
     c.ldCap = (size_t)DH_WORDS + (size_t)n + (size_t)maxP * (size_t)stride;
+    c.ldMaxP = maxP;
     c.ldMethod = 0;  // (not a valid plan until the launch below is built)
   }
   const size_t cap = c.ldCap;
@@ -2798,8 +2926,29 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
       for (int i = 0; i < n; i++) slot[(size_t)i] = i;
       HIPCHK(hipMemcpy(c.dpos, slot.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     }
+    const int nrows = c.ldMaxP;
+    if (lists) {
+      if (nrows < 1) throw KsError(KS_ERR_INTERNAL, "disrupt: the plan has no bound on NodeClaims");
+      if ((size_t)nrows > c.capDrows || !c.drows) {
+        if (c.drows) HIPCHK(hipFree(c.drows));
+        if (c.hrows) HIPCHK(hipHostFree(c.hrows));
+        c.drows = c.hrows = nullptr;
+        c.capDrows = 0;
+        HIPCHK(hipMalloc((void**)&c.drows, (size_t)nrows * sizeof(LaunchRow)));
+        HIPCHK(hipHostMalloc((void**)&c.hrows, (size_t)nrows * sizeof(LaunchRow), hipHostMallocDefault));
+        c.capDrows = (size_t)nrows;
+      }
+      launch_events(c);
+    }
     const std::function<void(hipStream_t)> tail = [&](hipStream_t st) {
       HIPCHK(disrupt_pick(c.L.lrec, c.recWords, c.L.lworks, c.dpos, n, d.R, d.TW, d.RSW, c.dout, (int)cap, st));
+      if (lists) {  // behind the pick on its stream, no host round trip: the grid is the plan's bound on NodeClaims
+        HIPCHK(hipMemsetAsync(c.drows, 0xFF, (size_t)nrows * sizeof(LaunchRow), st));
+        HIPCHK(hipEventRecord(c.evL[0], st));
+        HIPCHK(launch_lists_export(c.pb->dev, c.dout, n, (int)cap, c.pb->nameRank, nrows, c.drows, st));
+        HIPCHK(hipEventRecord(c.evL[1], st));
+        HIPCHK(hipMemcpyAsync(c.hrows, c.drows, (size_t)nrows * sizeof(LaunchRow), hipMemcpyDeviceToHost, st));
+      }
       // one copy: the header, the positions and the picked simulation's claims (at most cap words)
       HIPCHK(hipMemcpyAsync(c.hout, c.dout, cap * 4, hipMemcpyDeviceToHost, st));
     };
@@ -2846,6 +2995,16 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
       const int tpl = cl[0];
       if (tpl < 0 || tpl >= d.NTPL) throw KsError(KS_ERR_INTERNAL, "disrupt: NodeClaim template out of range");
       const std::vector<int> its = bits_to_its(h, tpl, cl + 3);
+      if (lists) {
+        if (k >= c.ldMaxP) throw KsError(KS_ERR_INTERNAL, "disrupt: more NodeClaims than the plan's bound");
+        const LaunchRow& row = c.hrows[k];
+        check_launch_row(h, tpl, cl + 3, row, "replacement " + std::to_string(k));
+        ks_cons::DisruptList l;
+        l.nopt = row.n_options;
+        l.its.assign(row.its, row.its + row.n_launch);
+        l.prices.assign(row.prices, row.prices + row.n_launch);
+        c.dl.push_back(std::move(l));
+      }
       int nopt = 0;
       for (int w = 0; w < d.TW; w++) nopt += __builtin_popcount((uint32_t)cl[3 + w]);
       if (nopt != cl[2] || nopt == 0 || (int)its.size() != nopt)
@@ -2857,6 +3016,7 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
       o += "{\"nodePoolName\":";
       ksjson::quote(o, h.tpls[(size_t)tpl].pool);
       o += ",\"instanceTypeOptions\":" + names_json(h, its);
+      if (lists) o += launch_fields_json(h, c.dl.back().its.data(), c.dl.back().prices.data(), (int)c.dl.back().its.size());
       o += ",\"requests\":" + claim_requests_json(h, simPods, tpl, creq.data());
       o += ",\"requirements\":[";
       const uint64_t pr = rs_present(rs);
@@ -2869,6 +3029,11 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
       }
       o += "]}";
     }
+  }
+  if (lists) {
+    c.dlValid = true;
+    // (the kernel's time when it computed a list: without a replacement every workgroup returned at once)
+    if (!c.dl.empty()) HIPCHK(hipEventElapsedTime(&c.launchMs, c.evL[0], c.evL[1]));
   }
   o += "]},\"sims\":[";
   // the simulations the reference runs: up to and including the pick (all of them with KS_CONS_ALL_SIMS)
@@ -3135,7 +3300,12 @@ int ks_cons_run(ks_cons* c, int rank, int world, const ks_solve_opts* opts, void
   DeviceGuard guard(c->pb->device, opts);
   c->passId++;  // (a decision's multi-node search is re-resolved for the new records)
   c->routes.clear();
-  const double ms = run_sims(*c, rank, world, records, records_on_device != 0);
+  const bool lists = opts && opts->launch_lists;
+  c->passLists = false;
+  c->launchMs = 0;
+  if (lists) require_launch_lists(c->pb.get());
+  const double ms = run_sims(*c, rank, world, records, records_on_device != 0, nullptr, lists, &c->launchMs);
+  c->passLists = lists;
   if (kernel_ms) *kernel_ms = ms;
   return KS_OK;
   API_CATCH
@@ -3235,6 +3405,61 @@ int ks_cons_claim_requirements(ks_cons* c, int sim, uint32_t* out) {
   API_CATCH
 }
 
+// The launch list of simulation `sim`'s Replace command from this handle's last run (the rank that ran it), after
+// the host's check of the row against the command's option words.
+int ks_cons_claim_launch(ks_cons* c, int sim, int32_t* instance_types, double* prices, int* n, int* n_options) {
+  API_TRY
+  if (!c) throw KsError(KS_ERR_ARG, "bad argument");
+  c->check_usable();
+  if (!c->passLists || !c->L.listed || !c->L.lrows)
+    throw KsError(KS_ERR_ARG, "the handle's last run did not set launch_lists");
+  DeviceGuard guard(c->pb->device, nullptr);
+  const Host& h = c->pb->host;
+  for (size_t k = 0; k < c->L.lsims.size(); k++)
+    if (c->L.lsims[k] == sim) {
+      std::vector<int32_t> rec((size_t)c->recWords);
+      HIPCHK(hipMemcpy(rec.data(), c->L.lrec + k * c->recWords, 4 * (size_t)c->recWords, hipMemcpyDeviceToHost));
+      check_record(h, rec.data(), "simulation " + std::to_string(sim));
+      if (rec[RF_ACTION] != CA_REPLACE) throw KsError(KS_ERR_ARG, "the simulation's action is not replace");
+      LaunchRow row;
+      HIPCHK(hipMemcpy(&row, c->L.lrows + k, sizeof row, hipMemcpyDeviceToHost));
+      const bool multi = sim >= 0 && sim < (int)c->sims.size() && c->sims[(size_t)sim].multi;
+      check_launch_row(h, rec[RF_TPL], rec.data() + RF_HDR + (multi ? 2 : 1) * h.dims.TW, row,
+                       "simulation " + std::to_string(sim));
+      if (instance_types) memcpy(instance_types, row.its, 4 * (size_t)row.n_launch);
+      if (prices) memcpy(prices, row.prices, 8 * (size_t)row.n_launch);
+      if (n) *n = row.n_launch;
+      if (n_options) *n_options = row.n_options;
+      return KS_OK;
+    }
+  throw KsError(KS_ERR_ARG, "simulation not in this rank's launch");
+  API_CATCH
+}
+
+// Replacement `i` of the handle's last ks_cons_disrupt (which set launch_lists); the arrays live until the next one.
+int ks_cons_disrupt_launch(const ks_cons* c, int i, const int32_t** instance_types, const double** prices, int* n,
+                           int* n_options) {
+  API_TRY
+  if (!c) throw KsError(KS_ERR_ARG, "bad argument");
+  if (!c->dlValid) throw KsError(KS_ERR_ARG, "the handle's last ks_cons_disrupt did not set launch_lists");
+  if (i < 0 || i >= (int)c->dl.size()) throw KsError(KS_ERR_ARG, "replacement index out of range");
+  const ks_cons::DisruptList& l = c->dl[(size_t)i];
+  if (instance_types) *instance_types = l.its.data();
+  if (prices) *prices = l.prices.data();
+  if (n) *n = (int)l.its.size();
+  if (n_options) *n_options = l.nopt;
+  return KS_OK;
+  API_CATCH
+}
+
+double ks_cons_launch_ms(const ks_cons* c) { return c ? (double)c->launchMs : 0; }
+
+const char* ks_cons_instance_type_name(const ks_cons* c, int instance_type) {
+  if (!c || !c->broken.empty() || !c->pb || instance_type < 0 || (size_t)instance_type >= c->pb->host.its.size())
+    return nullptr;
+  return c->pb->host.its[(size_t)instance_type].name.c_str();
+}
+
 int ks_cons_decide(ks_cons* c, const void* records, int world, int flags, const uint32_t* rs_table,
                    char** json_out) {
   return ks_cons_decide_clock(c, records, world, flags, rs_table, nullptr, json_out);
@@ -3266,8 +3491,20 @@ int ks_cons_decide_clock(ks_cons* c, const void* records, int world, int flags, 
       }
       return v.data();
     };
+    // the launch lists likewise, when the pass computed them (the rows are in this handle's launch)
+    std::map<int, LaunchRow> lcache;
+    const bool rowsHere = c->L.listed && c->L.lrows;
+    const LaunchFn launchOf = [&](int sim) -> const LaunchRow* {
+      if (!rowsHere || sim < 0 || sim >= (int)c->L.lsims.size() || c->L.lsims[(size_t)sim] != sim) return nullptr;
+      auto it = lcache.find(sim);
+      if (it == lcache.end()) {
+        it = lcache.emplace(sim, LaunchRow{}).first;
+        HIPCHK(hipMemcpy(&it->second, c->L.lrows + sim, sizeof(LaunchRow), hipMemcpyDeviceToHost));
+      }
+      return &it->second;
+    };
     *json_out = strdup(decide_json(*c, recs, world, all_sims, fetch, (flags & KS_CONS_CANDIDATES) != 0, clock,
-                                   (flags & KS_CONS_NO_SIMS) == 0)
+                                   (flags & KS_CONS_NO_SIMS) == 0, c->passLists ? &launchOf : nullptr)
                            .c_str());
     return KS_OK;
   }
@@ -3281,8 +3518,11 @@ int ks_cons_decide_clock(ks_cons* c, const void* records, int world, int flags, 
   std::map<int, const uint32_t*> table;
   for (size_t i = 0; i < need.size(); i++) table[need[i]] = rs_table + i * c->pb->host.dims.RSW;
   carry_walk(*c, recs, world, clock);  // (the cached walk when clock is null)
+  // (a pass with launch_lists: "sim" names the owner to ask, and a carried probe's list is local)
+  const LaunchFn noRows = [](int) -> const LaunchRow* { return nullptr; };
   *json_out = strdup(decide_json(*c, recs, world, all_sims, [&](int sim) { return table.at(sim); },
-                                 (flags & KS_CONS_CANDIDATES) != 0, clock, (flags & KS_CONS_NO_SIMS) == 0)
+                                 (flags & KS_CONS_CANDIDATES) != 0, clock, (flags & KS_CONS_NO_SIMS) == 0,
+                                 c->passLists ? &noRows : nullptr)
                          .c_str());
   return KS_OK;
   API_CATCH

@@ -34,4 +34,17 @@ constexpr size_t kLaunchMaxLds = 160 * 1024 - 2048;  // (the key table is static
 hipError_t launch_lists(const KsDev& D, const KsWork& W, const int32_t* it_name_rank, int nc, LaunchRow* rows,
                         hipStream_t st);
 
+// A consolidation pass's rows (k_launch_lists_sims): row k for launch slot k of `works` / `recs` (ns slots, recWords
+// words a record).  A slot whose record is a Replace gets the command's launch list: the options after
+// filterByPrice (after filterOutSameType for a multi-node prefix), NewNodeClaims[0]'s requirements, narrowed to spot
+// when the record says so.  Every other row keeps the caller's 0xFF fill.
+hipError_t launch_lists_sims(const KsDev& D, const KsWork* works, const int32_t* recs, int recWords,
+                             const int32_t* it_name_rank, int ns, LaunchRow* rows, hipStream_t st);
+
+// A Drift / Expiration pick's rows (k_launch_lists_export): row k for NodeClaim k of the buffer k_disrupt_pick wrote
+// (`out`, cap words, npos positions; ks_disrupt.h), enqueued behind it.  nrows bounds the grid (the plan's bound on
+// NodeClaims); rows past the exported claims, and all of them without a pick, keep the caller's 0xFF fill.
+hipError_t launch_lists_export(const KsDev& D, const int32_t* out, int npos, int cap, const int32_t* it_name_rank,
+                               int nrows, LaunchRow* rows, hipStream_t st);
+
 }  // namespace ks

@@ -182,6 +182,14 @@ struct DeviceGuard {
 // classes: also the request classes of a LEAN problem (a Solve handle; a consolidation handle has none)
 void ks_upload(ks_problem* pb, bool classes = false);
 
+// Launch lists (ks_capi.cpp): "" when every template's instance-type names are unique, else the refusal.
+std::string launch_names_refusal(const ks::Host& h);
+// What ks_cons_run and ks_cons_disrupt check first when ks_solve_opts.launch_lists is set: throws
+// KS_ERR_UNSUPPORTED for a template that lists one name twice (decided once per problem, pb->launchNames, which
+// ks_solve's own check of the same kind shares) and KS_ERR_CAPACITY for lists too long for the launch-list
+// kernels' LDS (a Solve tests that when it collects its Results).
+void require_launch_lists(ks_problem* pb);
+
 // Binary snapshots (ks_capi.cpp): a magic, the format version and the sizes of the shared structs.
 namespace ks { struct ArOut; struct ArIn; }
 void snapshot_header(ks::ArOut& a, const char magic[8]);

@@ -680,6 +680,15 @@ def _cons_lib():
         l.ks_cons_last_reruns.restype = ctypes.c_int
         l.ks_cons_last_routes.argtypes = [vp, ctypes.POINTER(vp)]
         l.ks_cons_disrupt.argtypes = [vp, ctypes.c_int, ctypes.POINTER(_Opts), ctypes.c_int, ctypes.POINTER(vp)]
+        l.ks_cons_claim_launch.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        l.ks_cons_disrupt_launch.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
+                                             ctypes.POINTER(ctypes.POINTER(ctypes.c_double)), ctypes.POINTER(ctypes.c_int),
+                                             ctypes.POINTER(ctypes.c_int)]
+        l.ks_cons_launch_ms.argtypes = [vp]
+        l.ks_cons_launch_ms.restype = ctypes.c_double
+        l.ks_cons_instance_type_name.argtypes = [vp, ctypes.c_int]
+        l.ks_cons_instance_type_name.restype = ctypes.c_char_p
         l.ks_cons_inspect_disrupt.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                               ctypes.c_int, ctypes.POINTER(vp)]
         l.ks_cons_encode_binary.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(vp),
@@ -800,8 +809,9 @@ class Consolidator:
         self.num_sims = l.ks_cons_num_sims(self._h)
         self._recbuf = None
 
-    def run(self, rank=0, world=1, device=-1, out_ptr=None, keep=False):
-        """Run this rank's simulations.  out_ptr: device pointer for records_per_rank*record_bytes
+    def run(self, rank=0, world=1, device=-1, out_ptr=None, keep=False, launch_lists=False):
+        """Run this rank's simulations.  launch_lists: also compute the launch list of every simulation whose
+        action is replace (claim_launch; decide() then reports them with the commands).  out_ptr: device pointer for records_per_rank*record_bytes
         bytes (e.g. a torch tensor's data_ptr()); None returns the records in host memory.
         Returns (records or None, kernel ms).
 
@@ -809,7 +819,7 @@ class Consolidator:
         overwrites (no copy per pass): a caller keeping one pass's records across the next run() must copy
         them (bytes(records))."""
         l = _cons_lib()
-        o = _Opts(device, 1, 1, 0, 0)
+        o = _Opts(device, 1, 1, 0, 0, 1 if launch_lists else 0)
         ms = ctypes.c_double()
         if keep:  # world 1: the records stay in the handle's pinned buffer; pass records=None to decide()
             _check(l.ks_cons_run(self._h, rank, world, ctypes.byref(o), None, 0, ctypes.byref(ms)))
@@ -846,6 +856,32 @@ class Consolidator:
         out = (ctypes.c_uint32 * max(l.ks_cons_requirement_words(self._h), 1))()
         _check(l.ks_cons_claim_requirements(self._h, sim, out))
         return bytes(out)
+
+    def _launch_names(self, ids):
+        l = _cons_lib()
+        return [l.ks_cons_instance_type_name(self._h, i).decode() for i in ids]
+
+    def claim_launch(self, sim):
+        """The launch list of simulation `sim`'s replace command after run(launch_lists=True), on the rank that ran
+        it (ks_cons_claim_launch): (instance-type names in OrderByPrice order cut to 100, their prices, the number
+        of options)."""
+        its, prices = (ctypes.c_int32 * 100)(), (ctypes.c_double * 100)()
+        n, nopt = ctypes.c_int(), ctypes.c_int()
+        _check(_cons_lib().ks_cons_claim_launch(self._h, sim, its, prices, ctypes.byref(n), ctypes.byref(nopt)))
+        return self._launch_names(its[:n.value]), list(prices[:n.value]), nopt.value
+
+    def disrupt_launch(self, i):
+        """The launch list of replacement `i` of the last disrupt(launch_lists=True) (ks_cons_disrupt_launch), as
+        claim_launch returns it."""
+        its, prices = ctypes.POINTER(ctypes.c_int32)(), ctypes.POINTER(ctypes.c_double)()
+        n, nopt = ctypes.c_int(), ctypes.c_int()
+        _check(_cons_lib().ks_cons_disrupt_launch(self._h, i, ctypes.byref(its), ctypes.byref(prices), ctypes.byref(n),
+                                                  ctypes.byref(nopt)))
+        return self._launch_names(its[:n.value]), list(prices[:n.value]), nopt.value
+
+    def launch_ms(self):
+        """HIP-event time of the launch-list kernel of the last run() / disrupt() (0 when none computed a list)."""
+        return _cons_lib().ks_cons_launch_ms(self._h)
 
     def decide(self, records, world=1, all_sims=False, fetch=None, candidates=True, clock=None, sims=True):
         """Sequential selection over the gathered records ([rank][slot] layout, bytes).  fetch(sim)
@@ -884,12 +920,13 @@ class Consolidator:
         _check(_cons_lib().ks_cons_validate(self._h, b, len(b), ctypes.byref(o), ctypes.byref(js)))
         return json.loads(_take_str(js))
 
-    def disrupt(self, method, all_sims=False, device=-1, lds_budget=0):
+    def disrupt(self, method, all_sims=False, device=-1, lds_budget=0, launch_lists=False):
         """Drift / Expiration ComputeCommand ("drift" | "expiration") on the handle's current state
         (ks_cons_disrupt): {"method", "candidates", "command": {"action", "candidates", "replacements"}, "sims",
-        "plan", "kernel_ms"}.  The pass's plan and records survive the call."""
+        "plan", "kernel_ms"}.  The pass's plan and records survive the call.  launch_lists: every replacement also
+        carries launchInstanceTypes / launchPrices (disrupt_launch reads them without JSON)."""
         js = ctypes.c_void_p()
-        o = _Opts(device, 1, 1, 0, lds_budget)
+        o = _Opts(device, 1, 1, 0, lds_budget, 1 if launch_lists else 0)
         _check(_cons_lib().ks_cons_disrupt(self._h, _method(method), ctypes.byref(o), 1 if all_sims else 0,
                                            ctypes.byref(js)))
         return json.loads(_take_str(js))
@@ -942,8 +979,8 @@ class Consolidator:
         buf = _records_buffer(records)
         return _cons_lib().ks_cons_records_alg_bytes(self._h, ctypes.cast(buf, ctypes.c_void_p), world)
 
-    def consolidate(self, all_sims=False, device=-1, clock=None):
-        recs, ms = self.run(0, 1, device)
+    def consolidate(self, all_sims=False, device=-1, clock=None, launch_lists=False):
+        recs, ms = self.run(0, 1, device, launch_lists=launch_lists)
         doc = self.decide(recs, 1, all_sims, clock=clock)
         doc["kernel_ms"] = ms
         return doc
