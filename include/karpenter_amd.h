@@ -434,12 +434,24 @@ int ks_cons_validate(ks_cons* c, const char* command_json, size_t len, const ks_
  * instanceTypeOptions, requests, requirements}]}, "sims": [{candidate, allNonPendingScheduled, newNodeClaims}],
  * "plan": {KO, KL, lds}, "kernel_ms"}; "sims" lists the simulations the reference would have run, up to and
  * including the pick (all of them with KS_CONS_ALL_SIMS in flags).  Requests are canonical Quantity text and the
- * requirements those after FinalizeScheduling (no hostname), as ks_results_json renders a Solve's NodeClaims.  A
- * simulation keeps no commit log, so the pods per replacement are not reported, and KS_ERR_UNSUPPORTED is returned
- * when the requests' text would depend on them (pods naming a resource in different quantity formats, or only
- * some pods naming it while its sum is zero). */
+ * requirements those after FinalizeScheduling (no hostname), as ks_results_json renders a Solve's NodeClaims.  The
+ * method's simulations keep no commit log, so without KS_CONS_PLACEMENTS the pods per replacement are not
+ * reported, and KS_ERR_UNSUPPORTED is returned when the requests' text would depend on them (pods naming a
+ * resource in different quantity formats, only some pods naming it while its sum is zero, or a problem with
+ * negative requests); the message names the flag.
+ * KS_CONS_PLACEMENTS in flags: when the command is replace, the picked simulation is run once more on an
+ * instantiation of the simulation kernel that stores its commit log (single-wave; one launch, in a launch of its
+ * own, appended to ks_cons_last_routes as "sims_log" / "sims_topo_log").  The re-run's record must equal the
+ * picked simulation's in every word a simulation writes, its log must place every pod at most once and agree with the device's pod
+ * count per NodeClaim and with the requests the device summed (a miss is KS_ERR_INTERNAL).  Every entry of
+ * "replacements" then gains "pods": [uid, ...] in commit order (NodeClaim.Pods), its "requests" are the Merge
+ * replayed over those pods with their recorded quantity formats (exact for mixed formats, partly named resources and
+ * negative requests: none of the three refusals applies), and the document gains "placements_ms", the HIP-event
+ * time of the re-run, before "kernel_ms".  delete and no-op commands launch nothing extra ("placements_ms": 0).
+ * Without the flag the document is byte for byte what it was.  opts->launch_lists may be combined with it. */
 #define KS_DISRUPT_EXPIRATION 1
 #define KS_DISRUPT_DRIFT 2
+#define KS_CONS_PLACEMENTS 8 /* flags of ks_cons_disrupt: pods per replacement, requests rendered from the commit log */
 /* With opts->launch_lists set every entry of "replacements" also carries "launchInstanceTypes" / "launchPrices":
  * its launch list, computed by a kernel enqueued behind the pick (no host round trip between them) and checked on
  * the host.  The refusals are ks_cons_run's.  The all-empty and no-pick commands have no replacement. */
@@ -449,6 +461,23 @@ int ks_cons_disrupt(ks_cons* c, int method, const ks_solve_opts* opts, int flags
  * set launch_lists. */
 int ks_cons_disrupt_launch(const ks_cons* c, int i, const int32_t** instance_types, const double** prices, int* n,
                            int* n_options);
+/* Simulation Results of one simulation of this handle's last ks_cons_run: the simulation is run once more with its
+ * commit log (as KS_CONS_PLACEMENTS does, with the same checks against the record the run left) and rendered as
+ * {"sim", "candidates": [names], "allNonPendingScheduled", "newNodeClaims": [{nodePoolName, instanceTypeOptions,
+ * requests, requirements, pods: [uid, ...]}], "existingNodes": [{name, pods: [uid, ...]}], "unscheduled": [uid, ...],
+ * "kernel_ms"}.  newNodeClaims are in the Solve's final order with pods in commit order; instanceTypeOptions,
+ * requests and requirements are as ks_results_json renders a Solve's NodeClaims after FinalizeScheduling;
+ * existingNodes lists only the nodes that received pods, in calculateExistingNodeClaims order; unscheduled are the
+ * simulation's pods (pending, then the candidates', then the deleting nodes') that no target holds.  No pod error
+ * texts.  `sim` indexes the handle's simulations, [0, ks_cons_num_sims): the multi-node prefixes first, largest
+ * first (the prefix of the first m candidates, m >= 2, is simulation num_sims - num_candidates - (m - 1)), then
+ * one per candidate in disruption-cost order (candidate i is simulation num_sims - num_candidates + i); it is the
+ * "sim" a replace command carries after a launch_lists run.  A command chosen from a carried multi-node probe
+ * ("sim": -1) has no simulation in the run and is out of scope.  opts: device and lds_budget (0: automatic).
+ * KS_ERR_ARG before the handle's first ks_cons_run, after a ks_cons_update until the next run, for a simulation the
+ * last run did not cover (another rank's) and for sim out of range.  The pass's plan and records survive; the
+ * launch is appended to ks_cons_last_routes ("family": "sims_log" or "sims_topo_log").  Free json_out with ks_free. */
+int ks_cons_sim_results(ks_cons* c, int sim, const ks_solve_opts* opts, char** json_out);
 /* Host-only, no device: {"method", "candidates": [names in the method's order], "empty": [the empty ones],
  * "transitionTimes": [seconds]} of the snapshot with update_json applied (NULL or "{}": none; an array: a sequence). */
 int ks_cons_inspect_disrupt(const char* snapshot_json, size_t len, const char* update_json, size_t ulen, int method,
@@ -477,10 +506,11 @@ int ks_cons_queue_readback(ks_cons* c, char** meta_json, int32_t** words, size_t
  * re-simulated from the carried relaxation states, one launch per probe (typically none). */
 int ks_cons_last_reruns(const ks_cons* c);
 /* The k_solve launches since this handle's last ks_cons_run began, in order, as a JSON list of
- * {"family": "sims" | "sims_topo" | "sims_mw" | "sims_mixed", "rt", "tl", "lean", "n"} (as "stats"."route" of
+ * {"family": "sims" | "sims_topo" | "sims_mw" | "sims_mixed" | "sims_log" | "sims_topo_log", "rt", "tl", "lean", "n"} (as "stats"."route" of
  * ks_results_json; "sims_mixed" adds "nmw", its leading simulations on 4-wave workgroups): the pass's own
  * launches (two when the long simulations run on a second stream, or a topology plan launches in two phases),
- * then one per carried-probe re-run of ks_cons_decide / ks_cons_needed_sims and per ks_cons_validate.
+ * then one per carried-probe re-run of ks_cons_decide / ks_cons_needed_sims, per ks_cons_validate, per
+ * ks_cons_disrupt (plus its logged re-run, "sims_log" / "sims_topo_log") and per ks_cons_sim_results.
  * Free with ks_free. */
 int ks_cons_last_routes(const ks_cons* c, char** json_out);
 /* Algorithmic bytes the gathered simulations scanned, summed from their records. */

@@ -32,7 +32,7 @@ void route_note(const Route& r) {
 RouteScope::RouteScope(std::vector<Route>* log) : prev(g_routes) { g_routes = log; }
 RouteScope::~RouteScope() { g_routes = prev; }
 static std::string route_json(const Route& r) {
-  static const char* fam[] = {"solve", "solve_topo", "sims", "sims_topo", "sims_mw", "sims_mixed"};
+  static const char* fam[] = {"solve", "solve_topo", "sims", "sims_topo", "sims_mw", "sims_mixed", "sims_log", "sims_topo_log"};
   std::string o = std::string("{\"family\":\"") + fam[r.family] + "\",\"rt\":" + std::to_string(r.rt) +
                   ",\"tl\":" + std::to_string(r.tl) + ",\"lean\":" + std::to_string(r.lean) + ",\"n\":" + std::to_string(r.n);
   if (r.family == KR_SIMS_MIXED) o += ",\"nmw\":" + std::to_string(r.nmw);

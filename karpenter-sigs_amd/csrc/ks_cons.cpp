@@ -368,6 +368,11 @@ struct ks_cons {
   Walk walk;
   uint64_t passId = 0;  // ks_cons_run calls (a walk is valid for the pass it was computed on)
   Launch LR;            // the re-runs' launch (its buffers are kept between re-runs)
+  // The logging re-run of one simulation (rerun_logged: KS_CONS_PLACEMENTS, ks_cons_sim_results) in a launch of its
+  // own.  slog: the launch being built / run is that one -- its workspace gets c_npods, it runs single-wave on the
+  // SLOG family (launch_simlog_plain / launch_simlog_topo), whatever route the pass took for the simulation
+  Launch LP;
+  bool slog = false;
   // Drift / Expiration (ks_cons_disrupt): the method's launch of one single-candidate simulation per candidate,
   // and the pick's output buffer (k_disrupt_pick writes it, one copy brings it to hout)
   Launch LD;
@@ -417,6 +422,7 @@ struct ks_cons {
     free_launch();
     LR.release();
     LD.release();
+    LP.release();
     if (dout) (void)hipFree(dout);
     if (dpos) (void)hipFree(dpos);
     if (hout) (void)hipHostFree(hout);
@@ -977,7 +983,7 @@ void prepare_launch(ks_cons& c, int rank, int world) {
   struct Off {
     size_t c_tpl, c_cnt, c_thr, c_host, c_req, c_max, c_rs, c_rem, order, n_req, n_rs, n_slot, queue, pod_state,
         last_len, log_pod, log_tgt, pod_status, pod_fstate, fail_code, fail_host, counters, rm, pool0, st_price, n_hp,
-        c_hp, tg_cnt, tg_ccnt, tg_cpos, tdel, tdead, tact, tmd, sstart, n_vslot, n_vc, vlog, vspec;
+        c_hp, c_npods, tg_cnt, tg_ccnt, tg_cpos, tdel, tdead, tact, tmd, sstart, n_vslot, n_vc, vlog, vspec;
   };
   std::vector<Off> offs(ns);
   std::vector<int> simP(ns), entBeg(ns + 1, 0);
@@ -1077,6 +1083,7 @@ void prepare_launch(ks_cons& c, int rank, int world) {
     o.counters = a.add(8 * CT_NCOUNTERS);
     o.n_hp = a.add(d.hpAny ? 8 * (size_t)N : 8);
     o.c_hp = a.add(8 * K);
+    o.c_npods = c.slog ? a.add(4 * K) : 0;
     o.rm = ai.add(4 * std::max<size_t>(sm.cands.size(), 1));
     o.pool0 = ai.add(8 * (size_t)NP * R);
     o.st_price = sm.multi ? ai.add(8 * (size_t)std::max(d.T, 1)) : 0;
@@ -1276,6 +1283,7 @@ void prepare_launch(ks_cons& c, int rank, int world) {
     w.counters = (int64_t*)(base + o.counters);
     w.n_hp = (uint64_t*)(base + o.n_hp);
     w.c_hp = (uint64_t*)(base + o.c_hp);
+    w.c_npods = c.slog ? (int32_t*)(base + o.c_npods) : nullptr;
     w.pod_map = c.L.lpodmap + entBeg[k];
     w.run_len = c.L.lrunlen + entBeg[k];
     w.P = simP[k];
@@ -1337,7 +1345,7 @@ void prepare_launch(ks_cons& c, int rank, int world) {
   const bool mwAuto = ns > 0 && (int64_t)c.L.lnent <= (int64_t)kMwChainRatio * simP[0];
   const bool mwWanted = mwEnv ? mwEnv[0] == '1' : mwAuto;
   c.L.lnmw = 0;
-  if (mwWanted && sims_mw_supported(pb.dev, c.L.lplan))
+  if (mwWanted && !c.slog && sims_mw_supported(pb.dev, c.L.lplan))
     while (c.L.lnmw < ns && simP[(size_t)c.L.lnmw] >= mwMin) c.L.lnmw++;
   c.L.pipeB = pipe;
   c.L.nA = pipe ? nA : 0;
@@ -1824,7 +1832,11 @@ double run_sims(ks_cons& c, int rank, int world, void* records, bool onDevice,
     HIPCHK(hipEventCreateWithFlags(&c.evFork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c.evJoin, hipEventDisableTiming));
   }
-  if (c.L.pipeB) {
+  if (c.slog) {
+    // the logging re-run: one launch on the single-wave SLOG routes (its plan has no 4-wave part and no second phase)
+    if (c.L.pipeB || c.L.lnmw) throw KsError(KS_ERR_INTERNAL, "logging re-run: the plan is not single-wave");
+    HIPCHK(launch_sims_logged(pb.dev, c.L.lworks, ns, c.L.lplan, pb.stream));
+  } else if (c.L.pipeB) {
     // a new topology plan: the multi-node prefixes start at once, the single-node simulations' inputs are built
     // while they run and launched on the second stream (they fill the CUs the long prefixes leave idle)
     if (!c.st2) {
@@ -2786,7 +2798,7 @@ std::string inspect_disrupt_json(const ks_cons& c, int method) {
 // naming it; a simulation where that does not hold is refused (KS_ERR_UNSUPPORTED) instead of guessed.
 std::string claim_requests_json(const Host& h, const std::vector<int>& simPods, int tpl, const int64_t* creq) {
   const KsDims& d = h.dims;
-  if (d.negReq) throw KsError(KS_ERR_UNSUPPORTED, "disrupt: negative requests (the requests' text needs the commit order)");
+  if (d.negReq) throw KsError(KS_ERR_UNSUPPORTED, "disrupt: negative requests (the requests' text needs the commit order: set KS_CONS_PLACEMENTS)");
   QList req;
   for (int r = 0; r < d.R; r++) {
     const bool tplHas = (h.tab.tpl_rmask[(size_t)tpl] >> r) & 1u;
@@ -2801,14 +2813,14 @@ std::string claim_requests_json(const Host& h, const std::vector<int>& simPods, 
     if (!present) {
       if (with > 0)
         throw KsError(KS_ERR_UNSUPPORTED, "disrupt: only some pods name resource " + h.resNames[(size_t)r] +
-                                              " (the requests' keys need the pods per NodeClaim)");
+                                              " (the requests' keys need the pods per NodeClaim: set KS_CONS_PLACEMENTS)");
       continue;
     }
     int fmt = (int)h.tab.tpl_rfmt[(size_t)tpl * d.R + r];
     if (h.tab.tpl_daemon[(size_t)tpl * d.R + r] == 0 && !fmts.empty()) {
       if (fmts.size() > 1)
         throw KsError(KS_ERR_UNSUPPORTED, "disrupt: pods write resource " + h.resNames[(size_t)r] +
-                                              " in more than one quantity format");
+                                              " in more than one quantity format (set KS_CONS_PLACEMENTS)");
       fmt = *fmts.begin();
     }
     Qty q = h.fromDev(r, creq[r]);
@@ -2827,8 +2839,270 @@ std::string claim_requests_json(const Host& h, const std::vector<int>& simPods, 
   return o + "}";
 }
 
+// One simulation run again with its commit log (k_solve<.., SIM, .., SLOG>, launch_sims_logged), read back and
+// checked: what KS_CONS_PLACEMENTS and ks_cons_sim_results render.  Pods are global indices.
+struct LoggedSim {
+  std::vector<int> simPods;  // pending + the candidates' + the deleting nodes' pods (the Solve's pod list)
+  std::vector<int32_t> rec, order, ctpl, chost;
+  std::vector<int64_t> creq;
+  std::vector<uint32_t> crem, crs;
+  std::vector<std::vector<int>> claimPods;                 // [claim id] in commit order (NodeClaim.Pods)
+  std::vector<std::pair<int, std::vector<int>>> nodePods;  // (host node, its new pods in commit order), by node
+  std::vector<int> unscheduled;                            // pods the log does not hold, in simPods order
+  int nc = 0;
+  double ms = 0;
+};
+
+// requests = Merge(daemon, RequestsForPods(pod_1), ...) replayed in commit order (resources.go:53-63) in device
+// units, as ks_solve does for a Solve's claims: Quantity.Add adopts the addend's format while the sum is zero, so
+// the text is exact for mixed formats, partly named resources and negative requests.  The sums must be the
+// device's (creq).
+std::string replay_requests_json(const Host& h, int tpl, const std::vector<int>& pods, const int64_t* creq,
+                                 const std::string& what) {
+  const KsDims& d = h.dims;
+  int64_t sum[kMaxR];
+  uint8_t fmt[kMaxR];
+  uint32_t present = h.tab.tpl_rmask[(size_t)tpl];
+  for (int r = 0; r < d.R; r++) {
+    sum[r] = h.tab.tpl_daemon[(size_t)tpl * d.R + r];
+    fmt[r] = h.tab.tpl_rfmt[(size_t)tpl * d.R + r];
+  }
+  for (int p : pods) {
+    const uint32_t m = h.tab.pod_rmask[(size_t)p];
+    present |= m;
+    for (uint32_t b = m; b; b &= b - 1) {
+      const int r = __builtin_ctz(b);
+      if (sum[r] == 0) fmt[r] = h.tab.pod_rfmt[(size_t)p * d.R + r];
+      sum[r] += h.tab.pod_req[(size_t)p * d.R + r];
+    }
+  }
+  std::string o = "{";
+  bool first = true;
+  for (int r = 0; r < d.R; r++) {  // resource ids are in name order
+    if (sum[r] != creq[r])
+      throw KsError(KS_ERR_INTERNAL, what + ": device requests diverge from the replayed Merge for " + h.resNames[(size_t)r] +
+                                         " (device " + std::to_string(creq[r]) + ", replay " + std::to_string(sum[r]) + ")");
+    if (!((present >> r) & 1u)) continue;
+    Qty q = h.fromDev(r, sum[r]);
+    q.f = (QFmt)fmt[r];
+    if (!first) o += ",";
+    first = false;
+    ksjson::quote(o, h.resNames[(size_t)r]);
+    o += ":";
+    ksjson::quote(o, qty_str(q));
+  }
+  return o + "}";
+}
+
+// sm: the simulation (indices into `cands` when given, else into the handle's candidates); want: its record from
+// the call that chose it.  The launch is LP's, so the pass's plan (L), the re-runs' (LR) and the methods' (LD) stay.
+// Before anything is rendered (a miss is KS_ERR_INTERNAL, as replay_check's for a Solve): the re-run's record equals
+// `want` in every word a simulation writes (a record holds no timing); the log places each of the simulation's pods at most once, on a
+// claim that exists or a node the simulation kept; per NodeClaim the logged pods number what the device counted
+// (KsWork::c_npods); the claim order is a permutation; the Merge of the logged pods' requests is c_req
+// (replay_requests_json, at rendering).
+LoggedSim rerun_logged(ks_cons& c, std::vector<ks_cons::Cand>* cands, const ks_cons::Sim& sm, size_t budget,
+                       const std::vector<int32_t>& want, const std::string& what) {
+  PhaseTimer pt("rerun_logged");
+  const Host& h = c.pb->host;
+  const KsDims& d = h.dims;
+  auto fail = [&](const std::string& m) { throw KsError(KS_ERR_INTERNAL, what + ": logged re-run check: " + m); };
+  LoggedSim out;
+  std::vector<ks_cons::Sim> one(1, sm);
+  int nPass = cands ? (int)cands->size() : c.nPass, multiHi = cands ? 0 : c.multiHi;
+  auto swapPlan = [&]() {
+    one.swap(c.sims);
+    if (cands) cands->swap(c.cands);
+    std::swap(nPass, c.nPass);
+    std::swap(multiHi, c.multiHi);
+  };
+  swapPlan();
+  std::swap(c.L, c.LP);
+  c.L.invalidate();  // a new plan every time, the buffers stay
+  const size_t budget0 = c.ldsBudget;
+  c.ldsBudget = budget;
+  c.slog = true;
+  auto restore = [&]() {
+    c.slog = false;
+    c.ldsBudget = budget0;
+    c.L.invalidate();
+    std::swap(c.L, c.LP);
+    swapPlan();
+  };
+  try {
+    std::vector<char> removed((size_t)std::max(d.N, 1), 0);
+    out.simPods = c.pending;
+    for (int ci : sm.cands) {
+      const ks_cons::Cand& k = c.cands[(size_t)ci];
+      out.simPods.insert(out.simPods.end(), k.pods.begin(), k.pods.end());
+      if (k.node >= 0 && k.node < d.N) removed[(size_t)k.node] = 1;
+    }
+    out.simPods.insert(out.simPods.end(), c.deleting.begin(), c.deleting.end());
+    out.rec.assign((size_t)c.recWords, 0);
+    out.ms = run_sims(c, 0, 1, out.rec.data(), false);
+    if (c.L.lhost.size() != 1) fail("the launch holds " + std::to_string(c.L.lhost.size()) + " simulations");
+    const KsWork w = c.L.lhost[0];
+    const int P = w.P, K = std::max(P, 1);
+    if (P != (int)out.simPods.size()) fail("the launch simulated " + std::to_string(P) + " pods");
+    if (want.size() != out.rec.size()) fail("record size");
+    // every word sim_record writes: the named header words [0, RF_NFIELDS) (RF_CLAIM only with a NodeClaim) and
+    // the option words from RF_HDR on; the header's padding [RF_NFIELDS, RF_HDR) is never written
+    const bool hasClaim = want[RF_NCLAIMS] > 0 && want[RF_ERROR] == KE_OK;
+    for (size_t i = 0; i < want.size(); i++)
+      if (want[i] != out.rec[i] && (i < RF_NFIELDS || i >= RF_HDR) && (i != RF_CLAIM || hasClaim))
+        fail("record word " + std::to_string(i) + " is " + std::to_string(out.rec[i]) + ", the chosen simulation's " +
+             std::to_string(want[i]));
+    if (out.rec[RF_ERROR] != KE_OK)
+      throw KsError(out.rec[RF_ERROR] == KE_CLAIM_CAP ? KS_ERR_CAPACITY : KS_ERR_INTERNAL,
+                    what + " reported kernel error " + std::to_string(out.rec[RF_ERROR]));
+    int64_t ctr[CT_ERROR + 1];
+    HIPCHK(hipMemcpy(ctr, w.counters, sizeof ctr, hipMemcpyDeviceToHost));
+    const int64_t nc = ctr[CT_NCLAIMS], nl = ctr[CT_NLOG];
+    if (ctr[CT_ERROR] != KE_OK || nc != out.rec[RF_NCLAIMS] || nc < 0 || nc > K || nl < 0 || nl > P)
+      fail("counters (" + std::to_string(nc) + " NodeClaims, " + std::to_string(nl) + " commits, error " +
+           std::to_string(ctr[CT_ERROR]) + ") against the record's " + std::to_string(out.rec[RF_NCLAIMS]) + " NodeClaims and " +
+           std::to_string(P) + " pods");
+    out.nc = (int)nc;
+    std::vector<int32_t> logp((size_t)nl), logt((size_t)nl), podmap((size_t)P), npods((size_t)nc);
+    auto dl = [&](auto& v, const void* src) {
+      if (!v.empty()) HIPCHK(hipMemcpy(v.data(), src, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost));
+    };
+    out.order.resize((size_t)nc);
+    out.ctpl.resize((size_t)nc);
+    out.chost.resize((size_t)nc);
+    out.creq.resize((size_t)nc * d.R);
+    out.crem.resize((size_t)nc * d.TW);
+    out.crs.resize((size_t)nc * d.RSW);
+    dl(out.order, w.order);
+    dl(out.ctpl, w.c_tpl);
+    dl(out.chost, w.c_host);
+    dl(out.creq, w.c_req);
+    dl(out.crem, w.c_rem);
+    dl(out.crs, w.c_rs);
+    dl(npods, w.c_npods);
+    dl(logp, w.log_pod);
+    dl(logt, w.log_tgt);
+    dl(podmap, w.pod_map);
+    pt.mark("launch + readback");
+    // the queue is the simulation's pods, each once
+    {
+      std::vector<int> a(out.simPods), b(podmap.begin(), podmap.end());
+      std::sort(a.begin(), a.end());
+      std::sort(b.begin(), b.end());
+      if (a != b) fail("the queue does not hold the simulation's pods");
+    }
+    std::vector<char> seen((size_t)nc, 0);
+    for (int k = 0; k < nc; k++) {
+      const int cl = out.order[(size_t)k];
+      if (cl < 0 || cl >= nc || seen[(size_t)cl]++) fail("NodeClaim order is not a permutation");
+      const int t = out.ctpl[(size_t)cl];
+      if (t < 0 || t >= d.NTPL) fail("NodeClaim " + std::to_string(cl) + " template out of range");
+    }
+    std::vector<char> placed((size_t)d.P, 0);
+    out.claimPods.assign((size_t)nc, {});
+    std::vector<std::vector<int>> byNode((size_t)std::max(d.N, 1));
+    for (int64_t i = 0; i < nl; i++) {
+      const int lp = logp[(size_t)i], t = logt[(size_t)i];
+      if (lp < 0 || lp >= P) fail("commit log pod index " + std::to_string(lp) + " out of range");
+      const int g = podmap[(size_t)lp];
+      if (placed[(size_t)g]++) fail("pod " + std::to_string(g) + " placed twice");
+      if (t >= 0) {
+        if (t >= nc) fail("commit log claim " + std::to_string(t) + " beyond " + std::to_string(nc));
+        out.claimPods[(size_t)t].push_back(g);
+      } else {
+        const int n = -t - 1;
+        if (n >= d.N || removed[(size_t)n]) fail("commit log node " + std::to_string(n) + " is not in the simulation");
+        byNode[(size_t)n].push_back(g);
+      }
+    }
+    for (int cl = 0; cl < nc; cl++)
+      if ((int)out.claimPods[(size_t)cl].size() != npods[(size_t)cl] || npods[(size_t)cl] < 1)
+        fail("NodeClaim " + std::to_string(cl) + " logged " + std::to_string(out.claimPods[(size_t)cl].size()) +
+             " pods, the device counted " + std::to_string(npods[(size_t)cl]));
+    for (int n = 0; n < d.N; n++)
+      if (!byNode[(size_t)n].empty()) out.nodePods.emplace_back(n, std::move(byNode[(size_t)n]));
+    for (int g : out.simPods)
+      if (!placed[(size_t)g]) out.unscheduled.push_back(g);
+    pt.mark("checks");
+  } catch (...) {
+    restore();
+    throw;
+  }
+  restore();
+  return out;
+}
+
+std::string uids_json(const Host& h, const std::vector<int>& pods) {
+  std::string o = "[";
+  for (size_t i = 0; i < pods.size(); i++) {
+    if (i) o += ",";
+    ksjson::quote(o, h.pods[(size_t)pods[i]].uid);
+  }
+  return o + "]";
+}
+
+// ks_cons_sim_results: simulation `sim` of the handle's last ks_cons_run, run again with its log.
+std::string sim_results_json(ks_cons& c, int sim, const ks_solve_opts* opts) {
+  const Host& h = c.pb->host;
+  const KsDims& d = h.dims;
+  if (c.L.lsims.empty() || c.L.lrank < 0)
+    throw KsError(KS_ERR_ARG, "sim_results: no ks_cons_run on this handle since it was created or last updated");
+  if (sim < 0 || sim >= (int)c.sims.size()) throw KsError(KS_ERR_ARG, "sim_results: simulation index out of range");
+  size_t slot = c.L.lsims.size();
+  for (size_t k = 0; k < c.L.lsims.size(); k++)
+    if (c.L.lsims[k] == sim) slot = k;
+  if (slot == c.L.lsims.size())
+    throw KsError(KS_ERR_ARG, "sim_results: the handle's last run did not cover this simulation (its rank is sim % world)");
+  std::vector<int32_t> want((size_t)c.recWords);
+  HIPCHK(hipMemcpy(want.data(), c.L.lrec + slot * (size_t)c.recWords, 4 * (size_t)c.recWords, hipMemcpyDeviceToHost));
+  const ks_cons::Sim sm = c.sims[(size_t)sim];
+  const size_t budget = opts && opts->lds_budget > 0 ? (size_t)opts->lds_budget : 0;
+  const std::string what = "simulation " + std::to_string(sim);
+  const LoggedSim ls = rerun_logged(c, nullptr, sm, budget, want, what);
+  std::string o = "{\"sim\":" + std::to_string(sim) + ",\"candidates\":[";
+  for (size_t i = 0; i < sm.cands.size(); i++) {
+    if (i) o += ",";
+    ksjson::quote(o, c.cands[(size_t)sm.cands[i]].name);
+  }
+  o += std::string("],\"allNonPendingScheduled\":") + ((ls.rec[RF_FLAGS] & RB_ALL_SCHEDULED) ? "true" : "false") +
+       ",\"newNodeClaims\":[";
+  for (int k = 0; k < ls.nc; k++) {
+    const int cl = ls.order[(size_t)k], tpl = ls.ctpl[(size_t)cl];
+    const int32_t* bits = (const int32_t*)ls.crem.data() + (size_t)cl * d.TW;
+    const std::vector<int> its = bits_to_its(h, tpl, bits);
+    if (its.empty()) throw KsError(KS_ERR_INTERNAL, what + ": NodeClaim without an instance type option");
+    const uint32_t* rs = ls.crs.data() + (size_t)cl * d.RSW;
+    if (k) o += ",";
+    o += "{\"nodePoolName\":";
+    ksjson::quote(o, h.tpls[(size_t)tpl].pool);
+    o += ",\"instanceTypeOptions\":" + names_json(h, its);
+    o += ",\"requests\":" + replay_requests_json(h, tpl, ls.claimPods[(size_t)cl], ls.creq.data() + (size_t)cl * d.R, what);
+    o += ",\"requirements\":[";
+    const uint64_t pr = rs_present(rs);
+    bool first = true;
+    for (int kk = 0; kk < d.NK; kk++) {  // FinalizeScheduling dropped the hostname requirement
+      if (!bit(pr, kk) || kk == h.hostKey) continue;
+      if (!first) o += ",";
+      first = false;
+      ksjson::quote(o, h.reqString(rs, kk, true, c.hostnameSeed + ls.chost[(size_t)cl]));
+    }
+    o += "],\"pods\":" + uids_json(h, ls.claimPods[(size_t)cl]) + "}";
+  }
+  o += "],\"existingNodes\":[";
+  for (size_t i = 0; i < ls.nodePods.size(); i++) {
+    if (i) o += ",";
+    o += "{\"name\":";
+    ksjson::quote(o, h.nodes[(size_t)ls.nodePods[i].first].name);
+    o += ",\"pods\":" + uids_json(h, ls.nodePods[i].second) + "}";
+  }
+  o += "],\"unscheduled\":" + uids_json(h, ls.unscheduled);
+  char buf[64];
+  snprintf(buf, sizeof buf, ",\"kernel_ms\":%.6f}", ls.ms);
+  return o + buf;
+}
+
 // Drift / Expiration ComputeCommand (drift.go:77-118, expiration.go:83-120) on the handle's current state.
-std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool allSims) {
+std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool allSims, bool placements) {
   PhaseTimer pt("ks_cons_disrupt");
   const Host& h = c.pb->host;
   const KsDims& d = h.dims;
@@ -2857,7 +3131,7 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
     if (anyEmpty) put_names(o, c, order, true);
     else o += "[]";
     c.dlValid = lists;  // (no replacement, nothing launched)
-    return o + ",\"replacements\":[]},\"sims\":[],\"kernel_ms\":0}";
+    return o + ",\"replacements\":[]},\"sims\":[]," + (placements ? "\"placements_ms\":0," : "") + "\"kernel_ms\":0}";
   }
   // the method's plan: one single-candidate simulation per candidate, in the method's order, in a launch of its
   // own (LD); the pass's candidates, simulations and launch come back afterwards
@@ -2985,8 +3259,23 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
   o += "\",\"candidates\":[";
   if (pick >= 0) ksjson::quote(o, c.candIn[(size_t)order[(size_t)pick]].k.name);
   o += "],\"replacements\":[";
+  double placementsMs = 0;
   if (pick >= 0 && nclaims > 0) {
     const ks_cons::CandIn& ci = c.candIn[(size_t)order[(size_t)pick]];
+    // KS_CONS_PLACEMENTS: the picked simulation once more, with its commit log (launch slot = position: dpos)
+    LoggedSim ls;
+    if (placements) {
+      std::vector<int32_t> want((size_t)c.recWords);
+      HIPCHK(hipMemcpy(want.data(), c.LD.lrec + (size_t)pick * c.recWords, 4 * (size_t)c.recWords, hipMemcpyDeviceToHost));
+      std::vector<ks_cons::Cand> one(1, ci.k);
+      one[0].pods = c.nodePods[(size_t)ci.k.node];
+      ks_cons::Sim sm;
+      sm.cands.assign(1, 0);
+      ls = rerun_logged(c, &one, sm, budget, want, "disrupt: the picked simulation");
+      placementsMs = ls.ms;
+      if (ls.nc != nclaims) throw KsError(KS_ERR_INTERNAL, "disrupt: the logged re-run has another NodeClaim count");
+      pt.mark("logged re-run");
+    }
     std::vector<int> simPods = c.pending;
     simPods.insert(simPods.end(), c.nodePods[(size_t)ci.k.node].begin(), c.nodePods[(size_t)ci.k.node].end());
     simPods.insert(simPods.end(), c.deleting.begin(), c.deleting.end());
@@ -3017,7 +3306,19 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
       ksjson::quote(o, h.tpls[(size_t)tpl].pool);
       o += ",\"instanceTypeOptions\":" + names_json(h, its);
       if (lists) o += launch_fields_json(h, c.dl.back().its.data(), c.dl.back().prices.data(), (int)c.dl.back().its.size());
-      o += ",\"requests\":" + claim_requests_json(h, simPods, tpl, creq.data());
+      int lc = -1;  // the re-run's claim at this position: the same claim state, word for word
+      if (placements) {
+        lc = ls.order[(size_t)k];
+        if (ls.ctpl[(size_t)lc] != tpl || ls.chost[(size_t)lc] != cl[1] ||
+            memcmp(ls.crem.data() + (size_t)lc * d.TW, cl + 3, 4 * (size_t)d.TW) != 0 ||
+            memcmp(ls.creq.data() + (size_t)lc * d.R, creq.data(), 8 * (size_t)d.R) != 0 ||
+            memcmp(ls.crs.data() + (size_t)lc * d.RSW, cl + 3 + d.TW + 2 * d.R, 4 * (size_t)d.RSW) != 0)
+          throw KsError(KS_ERR_INTERNAL, "disrupt: replacement " + std::to_string(k) + " differs in the logged re-run");
+        o += ",\"requests\":" + replay_requests_json(h, tpl, ls.claimPods[(size_t)lc], creq.data(),
+                                                    "disrupt: replacement " + std::to_string(k));
+      } else {
+        o += ",\"requests\":" + claim_requests_json(h, simPods, tpl, creq.data());
+      }
       o += ",\"requirements\":[";
       const uint64_t pr = rs_present(rs);
       bool first = true;
@@ -3027,7 +3328,9 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
         first = false;
         ksjson::quote(o, h.reqString(rs, kk, true, c.hostnameSeed + cl[1]));
       }
-      o += "]}";
+      o += "]";
+      if (placements) o += ",\"pods\":" + uids_json(h, ls.claimPods[(size_t)lc]);
+      o += "}";
     }
   }
   if (lists) {
@@ -3045,9 +3348,13 @@ std::string disrupt_json(ks_cons& c, int method, const ks_solve_opts* opts, bool
     o += std::string(",\"allNonPendingScheduled\":") + ((posw[i] & RB_ALL_SCHEDULED) ? "true" : "false") +
          ",\"newNodeClaims\":" + std::to_string(posw[i] >> 8) + "}";
   }
-  char buf[160];
-  snprintf(buf, sizeof buf, "],\"plan\":{\"KO\":%d,\"KL\":%d,\"lds\":%llu},\"kernel_ms\":%.6f}", plan.KO, plan.KL,
-           (unsigned long long)plan.lds, ms_);
+  char buf[224];
+  if (placements)
+    snprintf(buf, sizeof buf, "],\"plan\":{\"KO\":%d,\"KL\":%d,\"lds\":%llu},\"placements_ms\":%.6f,\"kernel_ms\":%.6f}",
+             plan.KO, plan.KL, (unsigned long long)plan.lds, placementsMs, ms_);
+  else
+    snprintf(buf, sizeof buf, "],\"plan\":{\"KO\":%d,\"KL\":%d,\"lds\":%llu},\"kernel_ms\":%.6f}", plan.KO, plan.KL,
+             (unsigned long long)plan.lds, ms_);
   return o + buf;
 }
 
@@ -3328,7 +3635,17 @@ int ks_cons_disrupt(ks_cons* c, int method, const ks_solve_opts* opts, int flags
   if (!c || !json_out) throw KsError(KS_ERR_ARG, "null argument");
   c->check_usable();
   DeviceGuard guard(c->pb->device, opts);
-  *json_out = strdup(disrupt_json(*c, method, opts, (flags & KS_CONS_ALL_SIMS) != 0).c_str());
+  *json_out = strdup(disrupt_json(*c, method, opts, (flags & KS_CONS_ALL_SIMS) != 0, (flags & KS_CONS_PLACEMENTS) != 0).c_str());
+  return KS_OK;
+  API_CATCH
+}
+
+int ks_cons_sim_results(ks_cons* c, int sim, const ks_solve_opts* opts, char** json_out) {
+  API_TRY
+  if (!c || !json_out) throw KsError(KS_ERR_ARG, "null argument");
+  c->check_usable();
+  DeviceGuard guard(c->pb->device, opts);
+  *json_out = strdup(sim_results_json(*c, sim, opts).c_str());
   return KS_OK;
   API_CATCH
 }

@@ -101,7 +101,7 @@ struct Plan {
 
 // The k_solve instantiation one launch picked (ks_solve.hip: launch_family, launch_sims_mw, launch_sims_mixed),
 // noted on the host at the launch site for the caller's route log (ks_runtime.h RouteScope).
-enum RouteFamily { KR_SOLVE = 0, KR_SOLVE_TOPO, KR_SIMS, KR_SIMS_TOPO, KR_SIMS_MW, KR_SIMS_MIXED };
+enum RouteFamily { KR_SOLVE = 0, KR_SOLVE_TOPO, KR_SIMS, KR_SIMS_TOPO, KR_SIMS_MW, KR_SIMS_MIXED, KR_SIMS_LOG, KR_SIMS_TOPO_LOG };
 struct Route {
   int32_t family;  // RouteFamily
   int32_t rt;      // the RT template argument: 3, 4, or 0 (the generic code)
@@ -274,7 +274,9 @@ enum RecField {
   RF_ERROR,         // KernelError of the simulation's Solve
   RF_ALGB_LO,       // algorithmic bytes the simulation scanned, low / high word
   RF_ALGB_HI,
-  RF_CLAIM,         // claim id of NewNodeClaims[0] in the simulation's workspace (its requirements stay there)
+  RF_CLAIM,         // claim id of NewNodeClaims[0] in the simulation's workspace (its requirements stay there);
+                    // written only when the simulation has a NodeClaim and no kernel error
+  RF_NFIELDS,       // the named header words end here: words [RF_NFIELDS, RF_HDR) are padding no kernel writes
   RF_HDR = 16,      // then: [TW] options, [TW] after filterByPrice, [TW] after filterOutSameType
 };
 // RB_RELAXED: Preferences.Relax changed some pod of the simulation (the pod objects a multi-node probe relaxes
@@ -353,6 +355,9 @@ struct KsWork {
   // past the queue window while the queue was still NewQueue's order; k_log_expand writes its log entries.  A record
   // places at least one pod and a pod is popped once before the first push-back, so P records always suffice.
   int32_t KS_G* run_log;    // [P][4]
+  // A logging re-run of one simulation (k_solve<.., SIM, .., SLOG>, ks_simlog.hip): len(Pods) per claim id, written
+  // by the epilogue beside the commit log; null in every other launch
+  int32_t KS_G* c_npods;    // [Kcap]
 };
 
 enum Counter {

@@ -17,6 +17,8 @@ hipError_t launch_solve(const KsDev& D, const KsWork* works_dev, int nrep, const
                         hipEvent_t mid, const int32_t* fixed_order = nullptr, hipEvent_t* feas = nullptr,
                         int32_t* run_len = nullptr, uint64_t* run_words = nullptr, hipEvent_t post = nullptr);
 hipError_t launch_sims(const KsDev& D, const KsWork* works_dev, int nsims, const Plan& pl, hipStream_t st);
+// ... on the instantiations that store the commit log (ks_simlog.hip, ks_simlog_topo.hip): single-wave routes only
+hipError_t launch_sims_logged(const KsDev& D, const KsWork* works_dev, int nsims, const Plan& pl, hipStream_t st);
 // The topology simulations' kernel alone, and the feasibility launches launch_sims makes before it (a two-phase
 // consolidation plan, ks_cons.cpp run_sims).
 hipError_t launch_sims_topo(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st);

@@ -1297,7 +1297,7 @@ static __device__ __noinline__ uint32_t claim_sort_general_out(LI32 okey, LI32 o
   return claim_sort_general<true, true>(okey, order, n, pivot);
 }
 
-template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN>
+template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN, bool SLOG = false>
 struct Solver : ClaimSort {
   static constexpr int RM = RT > 0 ? RT : kMaxR;
   // LEAN: the problem uses none of host ports, limited volumes, pod label requirements, shared UIDs,
@@ -1470,9 +1470,10 @@ struct Solver : ClaimSort {
   static constexpr bool LOG_RUNS = KS_LOG_RUNS && KS_CLAIM_RUNS && LEAN && !SIM;
   int lg_lo = 0;
   int runRecs = 0;
-  // (A simulation's placements are never read back -- the host reads its record -- so SIM only counts them.)
+  // (A pass's simulations only count their placements: the host reads their records.  SLOG: the re-run of one
+  // simulation whose placements the host renders stores them as a Solve does, ks_simlog.hip.)
   __device__ __forceinline__ void log_commit(int p, int tgt, int& nlog) {
-    if constexpr (SIM) {
+    if constexpr (SIM && !SLOG) {
       nlog++;
       return;
     }
@@ -1490,8 +1491,10 @@ struct Solver : ClaimSort {
     }
   }
   // Commit-log entries for `n` (<= 64) placements at once: lane t holds entry nlog + t (pod, target).
+  // Its callers are the NodeClaim runs, which are a Solve's alone (LEAN && !SIM): no SLOG instantiation reaches it
+  // (a logged simulation's pods all go through log_commit), so the gate below only keeps the three functions alike.
   __device__ __forceinline__ void log_batch(int n, int pod_t, int tgt_t, int& nlog) {
-    if constexpr (SIM) {
+    if constexpr (SIM && !SLOG) {
       nlog += n;
       return;
     }
@@ -1517,7 +1520,7 @@ struct Solver : ClaimSort {
     nlog += n;
   }
   __device__ __forceinline__ void log_flush(int nlog) {
-    if constexpr (SIM) return;
+    if constexpr (SIM && !SLOG) return;
     const int k = nlog & (kWave - 1);
     if (lane() < k && (!LOG_RUNS || lane() >= lg_lo)) {
       W.log_pod[nlog - k + lane()] = lg_p;
@@ -3730,7 +3733,7 @@ __device__ __forceinline__ void mw_helper(const KsDev& D, const KsWork& W, LU32 
   }
 }
 
-template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN, bool MW = false>
+template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN, bool MW = false, bool SLOG = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, MW ? 256 : 64))) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_solve(KsDev D, const KsWork* works, Plan pl) {
 #define KS_BODY_WORK ((const KsWork KS_C*)works)[blockIdx.x]
 #define KS_BODY_SMEM_DECL                                             \
@@ -3742,7 +3745,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, MW ? 256 : 64))) __attr
 }
 
 // The same body for one simulation of a mixed launch (k_sim_mixed): work item widx, LDS at smem_in.
-template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN, bool MW>
+template <int RT, bool TL, bool SIM, bool TOPO, bool LEAN, bool MW, bool SLOG = false>
 __device__ __forceinline__ void solve_body(const KsDev& D, const KsWork* works, const Plan& pl, int widx,
                                            char KS_L* smem_in) {
 #define KS_BODY_WORK ((const KsWork KS_C*)works)[widx]
@@ -3771,13 +3774,18 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 256))) __attribute__((a
 
 // Every translation unit instantiates one k_solve family (KS_TU 0: Solve, 1: Solve + topology,
 // 2: simulations, 3: simulations + topology; ks_solve_topo.hip / ks_sim.hip / ks_sim_topo.hip
-// include this file), so the four compile in parallel.
-template <bool SIM, bool TOPO>
+// include this file), so the four compile in parallel.  KS_TU 4 / 5 (ks_simlog.hip / ks_simlog_topo.hip) are the
+// simulation families again with SLOG: the commit log is stored, for the re-run of one simulation whose placements
+// the host renders (ks_cons.cpp rerun_logged).  Those are the single-wave routes only.
+template <bool SIM, bool TOPO, bool SLOG = false>
 hipError_t launch_family(const KsDev& D, const KsWork* works_dev, int n, const Plan& pl, hipStream_t st) {
 #define KS_LAUNCH(RT_, TL_, LEAN_)                                                                                 \
   do {                                                                                                             \
-    route_note(Route{SIM ? (TOPO ? KR_SIMS_TOPO : KR_SIMS) : (TOPO ? KR_SOLVE_TOPO : KR_SOLVE), RT_, TL_, LEAN_, n, 0}); \
-    hipLaunchKernelGGL((k_solve<RT_, TL_, SIM, TOPO, LEAN_>), dim3(n), dim3(kWave), pl.lds, st, D, works_dev, pl); \
+    route_note(Route{SIM ? (SLOG ? (TOPO ? KR_SIMS_TOPO_LOG : KR_SIMS_LOG) : (TOPO ? KR_SIMS_TOPO : KR_SIMS))          \
+                         : (TOPO ? KR_SOLVE_TOPO : KR_SOLVE),                                                      \
+                     RT_, TL_, LEAN_, n, 0});                                                                      \
+    hipLaunchKernelGGL((k_solve<RT_, TL_, SIM, TOPO, LEAN_, false, SLOG>), dim3(n), dim3(kWave), pl.lds, st, D,    \
+                       works_dev, pl);                                                                             \
   } while (0)
   if (n <= 0) return hipSuccess;  // e.g. a consolidation pass with no candidates: nothing to simulate
   const bool tl = pl.talloc != 0;
@@ -3798,6 +3806,8 @@ hipError_t launch_sims_plain(const KsDev& D, const KsWork* w, int n, const Plan&
 hipError_t launch_sims_topo(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st);
 hipError_t launch_sims_mw(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st);
 hipError_t launch_sims_mixed(const KsDev& D, const KsWork* w, int n, int nmw, const Plan& pl, hipStream_t st);
+hipError_t launch_simlog_plain(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st);
+hipError_t launch_simlog_topo(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st);
 
 #if KS_TU == 1
 hipError_t launch_solve_topo(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st) {
@@ -3841,6 +3851,14 @@ hipError_t launch_sims_mw(const KsDev& D, const KsWork* w, int n, const Plan& pl
 #elif KS_TU == 3
 hipError_t launch_sims_topo(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st) {
   return launch_family<true, true>(D, w, n, pl, st);
+}
+#elif KS_TU == 4
+hipError_t launch_simlog_plain(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st) {
+  return launch_family<true, false, true>(D, w, n, pl, st);
+}
+#elif KS_TU == 5
+hipError_t launch_simlog_topo(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st) {
+  return launch_family<true, true, true>(D, w, n, pl, st);
 }
 #else
 hipError_t launch_solve_plain(const KsDev& D, const KsWork* w, int n, const Plan& pl, hipStream_t st) {
@@ -4192,6 +4210,14 @@ hipError_t launch_sims(const KsDev& D, const KsWork* works_dev, int nsims, const
   if (D.d.fmOn) launch_feasibility(D, st);
   if (D.d.fnOn) launch_feasibility_nodes(D, st);
   return (D.d.G ? launch_sims_topo : launch_sims_plain)(D, works_dev, nsims, pl, st);
+}
+// launch_sims on the logging instantiations (SLOG: the commit log is stored; KsWork::c_npods must be set).
+hipError_t launch_sims_logged(const KsDev& D, const KsWork* works_dev, int nsims, const Plan& pl, hipStream_t st) {
+  if (pl.lds > 160 * 1024) return hipErrorInvalidValue;
+  if (nsims <= 0) return hipSuccess;
+  if (D.d.fmOn) launch_feasibility(D, st);
+  if (D.d.fnOn) launch_feasibility_nodes(D, st);
+  return (D.d.G ? launch_simlog_topo : launch_simlog_plain)(D, works_dev, nsims, pl, st);
 }
 bool sims_mw_supported(const KsDev& D, const Plan& pl) {
   return !D.d.G && D.d.lean && pl.talloc && D.d.N > 0 && pl.lds + kMwBytes <= 160 * 1024 && (D.d.R == 3 || D.d.R == 4);

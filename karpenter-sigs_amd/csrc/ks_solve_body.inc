@@ -1,7 +1,7 @@
 // The body of k_solve (ks_solve.hip): one simulation or Solve per wavefront (MW: per 4-wave workgroup).
 // Included by the k_solve kernel and by solve_body (the mixed simulation launch), which define
 // KS_BODY_WORK (this workgroup's / wave's KsWork) and KS_BODY_SMEM_DECL (its LDS base `smem`).
-  constexpr int RM = Solver<RT, TL, SIM, TOPO, LEAN>::RM;
+  constexpr int RM = Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::RM;
   // The loop's branch conditions are forced scalar (ub / uni): its control flow is wave-uniform by
   // construction, and left to prove that itself the compiler falls back to exec-masked code for the whole
   // commit loop, which costs time and, in one build of the requirement-carrying instantiation, lost a
@@ -22,7 +22,7 @@
   KS_BODY_SMEM_DECL
   const KsWork KS_C& W = KS_BODY_WORK;
   const KsDims& d = D.d;
-  Solver<RT, TL, SIM, TOPO, LEAN> S(D, W, pl);
+  Solver<RT, TL, SIM, TOPO, LEAN, SLOG> S(D, W, pl);
   const int R = S.R();
   char KS_L* sp = smem;
   auto take = [&](size_t bytes) { char KS_L* r = sp; sp += (bytes + 15) & ~(size_t)15; return r; };
@@ -49,19 +49,19 @@
   S.s_fic = (LU32)take(4 * (size_t)d.TW + 8);
   S.s_fof = (LU32)take(4 * (size_t)d.TW + 8);
   S.s_firr = (LU32)take(4 * (size_t)d.TW + 8);
-  constexpr bool MEMO = Solver<RT, TL, SIM, TOPO, LEAN>::TPL_MEMO;
+  constexpr bool MEMO = Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::TPL_MEMO;
   S.s_memo = (LU32)take(MEMO ? 4 * (size_t)tpl_memo_words(R, d.TW) : 0);
   if constexpr (MEMO) S.s_memo[S.MM_T] = (uint32_t)-1;  // empty (wave-wide store of a uniform value)
-  constexpr bool MASKS = Solver<RT, TL, SIM, TOPO, LEAN>::TPL_MASKS;
+  constexpr bool MASKS = Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::TPL_MASKS;
   S.s_tmask = (LU32)take(MASKS && pl.tmask ? 4 * (size_t)tpl_mask_words(d.NTPL, d.TW) : 0);
   S.s_tmv = (LU32)take(MASKS && pl.tmask ? 4 * (size_t)d.NTPL : 0);
   if constexpr (MASKS) {
     if (pl.tmask)
       for (int i = lane(); i < d.NTPL; i += kWave) S.s_tmv[i] = 0;  // no row filled yet
   }
-  constexpr bool CAPB = Solver<RT, TL, SIM, TOPO, LEAN>::CAP_BOUND;
-  constexpr bool CHAINB = Solver<RT, TL, SIM, TOPO, LEAN>::RUN_CHAIN;
-  constexpr bool FRONT = Solver<RT, TL, SIM, TOPO, LEAN>::RUN_FRONT;
+  constexpr bool CAPB = Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::CAP_BOUND;
+  constexpr bool CHAINB = Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::RUN_CHAIN;
+  constexpr bool FRONT = Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::RUN_FRONT;
   S.s_fbeg = (LI32)take(FRONT ? 4 * (size_t)(d.NTPL + 1) : 0);
   S.s_front = (LI32)take(FRONT ? 4 * (size_t)D.frontTotal : 0);
   const int NWN = (d.N + 31) >> 5;
@@ -69,9 +69,9 @@
   S.s_tch = (LU32)take(SIM ? 4 * (size_t)NWN : 0);
   S.s_tchr = (LU32)take(SIM || d.fnOn ? 4 * (size_t)NWN : 0);
   S.s_tvol = (LU32)take(SIM ? 4 * (size_t)NWN : 0);
-  S.s_vol = (LI32)take(!LEAN && d.volAny ? 4 * (size_t)Solver<RT, TL, SIM, TOPO, LEAN>::VO_WORDS : 0);
+  S.s_vol = (LI32)take(!LEAN && d.volAny ? 4 * (size_t)Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::VO_WORDS : 0);
   if (!LEAN && d.volAny)
-    for (int i = lane(); i < Solver<RT, TL, SIM, TOPO, LEAN>::VO_WORDS; i += kWave) S.s_vol[i] = 0;
+    for (int i = lane(); i < Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::VO_WORDS; i += kWave) S.s_vol[i] = 0;
   S.s_tgm = (LI32)take(4 * (size_t)d.G * TGM_WORDS);
   S.s_tmin = (LI32)take(4 * (size_t)d.G);
   S.s_trs0 = (LU32)take(d.G ? 4 * (size_t)d.RSW : 0);
@@ -285,7 +285,7 @@
   bool srt = true;      // s.newNodeClaims non-decreasing in len(Pods)
   // the sorted position whose count increment left the pending descent (!srt); -1: an appended claim, or not
   // tracked (sort_claims' closed form, KS_SORT_CLOSED)
-  constexpr bool SORTC = Solver<RT, TL, SIM, TOPO, LEAN>::SORT_CLOSED;
+  constexpr bool SORTC = Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::SORT_CLOSED;
   int dpos = -1;
   bool dapp = false;  // ... and that it is an appended claim's (try_templates left it)
   int64_t sortsClosed = 0;
@@ -373,7 +373,9 @@
       // next pops each fit a node of the register window, the step is Queue.Pop + the window's
       // first-fit ballots + the commit to the owner lane's registers, with nothing else live.  A pod
       // that fits no window node (or a stale queue) leaves it un-popped for the general step below.
-      // (A simulation's placements are not read back -- its record is -- so nothing is logged here.)
+      // (A simulation's placements are not read back -- its record is -- so nothing is logged here.  SLOG, the
+      // re-run whose placements are: every pod takes the single-pod step below, which logs it; a run places its
+      // pods on the same nodes in the same order, so the record is the same.)
       if (d.N > 0) {
         while (wi < wn) {
           const uint64_t fll = (uint64_t)rdl64((int64_t)w.ll, wi);
@@ -407,7 +409,7 @@
             m = (nr ? ctz64(nr) : kWave) - wi;
           }
           m = uni(m);
-          if (m >= KS_RUN_MIN) {
+          if (!SLOG && m >= KS_RUN_MIN) {
             PH_BEGIN(tb);
             float rq[RM];
 #pragma unroll
@@ -534,7 +536,8 @@
           }
           if ((rdl(nfv, owner) & NF_UNUSABLE) && !(fpf & PF_PROVISIONABLE)) allSched = false;
           if (rdl(w.st, wi) == ST_FAILED) W.pod_status[fpod] = ST_SCHEDULED;  // (wave-wide, uniform)
-          nlog++;
+          if constexpr (SLOG) S.log_commit(fpod, -(j + 1), nlog);
+          else nlog++;
           S.algbytes += (int64_t)(j + 1) * (16 * R + 16);
           qhead = qhead + 1 == P ? 0 : qhead + 1;
           qlen--;
@@ -1218,7 +1221,7 @@
                     if (wi + k <= wn) {  // the run's pods are the window's next lanes
                       const int src = wi + lane() < kWave ? wi + lane() : kWave - 1;
                       S.log_batch(k, __shfl(w.p, src), c, nlog);
-                    } else if constexpr (Solver<RT, TL, SIM, TOPO, LEAN>::LOG_RUNS) {
+                    } else if constexpr (Solver<RT, TL, SIM, TOPO, LEAN, SLOG>::LOG_RUNS) {
                       // past the window: nothing was pushed back yet (only an ident run reaches here), so the run's
                       // pods are NewQueue's order from qhead on and one record describes its entries
                       S.log_run_record(k, qhead, c, nlog);
@@ -1384,6 +1387,12 @@
   S.log_flush(nlog);
   // write back LDS-resident claim state for the host
   for (int i = lane(); i < nclaims; i += kWave) W.order[i] = S.s_order[i];
+  if constexpr (SLOG) {  // len(Pods) per claim id, for the host's check of the log (the workspace holds max(P, 1) claims)
+    for (int i = lane(); i < nclaims; i += kWave) {
+      const int c = S.s_order[i];
+      if (c >= 0 && c < (P > 1 ? P : 1)) W.c_npods[c] = S.s_okey[i];
+    }
+  }
   const int kl = nclaims < pl.KL ? nclaims : pl.KL;
   for (int i = lane(); i < kl * R; i += kWave) W.c_req[i] = S.lc.req[i];
   for (int i = lane(); i < kl * d.TW; i += kWave) W.c_rem[i] = S.lc.rem[i];

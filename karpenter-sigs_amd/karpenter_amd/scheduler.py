@@ -680,6 +680,7 @@ def _cons_lib():
         l.ks_cons_last_reruns.restype = ctypes.c_int
         l.ks_cons_last_routes.argtypes = [vp, ctypes.POINTER(vp)]
         l.ks_cons_disrupt.argtypes = [vp, ctypes.c_int, ctypes.POINTER(_Opts), ctypes.c_int, ctypes.POINTER(vp)]
+        l.ks_cons_sim_results.argtypes = [vp, ctypes.c_int, ctypes.POINTER(_Opts), ctypes.POINTER(vp)]
         l.ks_cons_claim_launch.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         l.ks_cons_disrupt_launch.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
@@ -719,6 +720,7 @@ def inspect_consolidation_update(snapshot, update=None):
 
 
 DISRUPT_METHODS = {"expiration": 1, "drift": 2}  # KS_DISRUPT_EXPIRATION / KS_DISRUPT_DRIFT
+KS_CONS_PLACEMENTS = 8  # ks_cons_disrupt flag: pods per replacement, requests rendered from the commit log
 
 
 def _method(method):
@@ -920,15 +922,29 @@ class Consolidator:
         _check(_cons_lib().ks_cons_validate(self._h, b, len(b), ctypes.byref(o), ctypes.byref(js)))
         return json.loads(_take_str(js))
 
-    def disrupt(self, method, all_sims=False, device=-1, lds_budget=0, launch_lists=False):
+    def disrupt(self, method, all_sims=False, device=-1, lds_budget=0, launch_lists=False, placements=False):
         """Drift / Expiration ComputeCommand ("drift" | "expiration") on the handle's current state
         (ks_cons_disrupt): {"method", "candidates", "command": {"action", "candidates", "replacements"}, "sims",
         "plan", "kernel_ms"}.  The pass's plan and records survive the call.  launch_lists: every replacement also
-        carries launchInstanceTypes / launchPrices (disrupt_launch reads them without JSON)."""
+        carries launchInstanceTypes / launchPrices (disrupt_launch reads them without JSON).  placements
+        (KS_CONS_PLACEMENTS): a replace command's picked simulation runs once more with its commit log; every
+        replacement gains "pods" (UIDs in commit order), its "requests" are rendered from the log (no refusal for
+        mixed quantity formats), and the document gains "placements_ms"."""
         js = ctypes.c_void_p()
         o = _Opts(device, 1, 1, 0, lds_budget, 1 if launch_lists else 0)
-        _check(_cons_lib().ks_cons_disrupt(self._h, _method(method), ctypes.byref(o), 1 if all_sims else 0,
-                                           ctypes.byref(js)))
+        flags = (1 if all_sims else 0) | (KS_CONS_PLACEMENTS if placements else 0)
+        _check(_cons_lib().ks_cons_disrupt(self._h, _method(method), ctypes.byref(o), flags, ctypes.byref(js)))
+        return json.loads(_take_str(js))
+
+    def sim_results(self, sim, device=-1, lds_budget=0):
+        """Simulation Results of simulation `sim` of the last run() (ks_cons_sim_results): {"sim", "candidates",
+        "allNonPendingScheduled", "newNodeClaims": [{nodePoolName, instanceTypeOptions, requests, requirements,
+        pods}], "existingNodes": [{name, pods}], "unscheduled", "kernel_ms"}, pods as UIDs in commit order.  The
+        simulation runs once more with its commit log; KsError (KS_ERR_ARG) before the first run, after update()
+        until the next run, for another rank's simulation and for `sim` out of range."""
+        js = ctypes.c_void_p()
+        o = _Opts(device, 1, 1, 0, lds_budget, 0)
+        _check(_cons_lib().ks_cons_sim_results(self._h, sim, ctypes.byref(o), ctypes.byref(js)))
         return json.loads(_take_str(js))
 
     def sim_counters(self, sim):

@@ -15,7 +15,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "karpenter-sigs_amd", "build")
 LLVM = "/opt/rocm/lib/llvm/bin"
-TUS = ["ks_solve", "ks_solve_topo", "ks_sim", "ks_sim_topo", "ks_queue", "ks_feas"]
+TUS = ["ks_solve", "ks_solve_topo", "ks_sim", "ks_sim_topo", "ks_simlog", "ks_simlog_topo", "ks_queue", "ks_feas"]
 FIELDS = [".sgpr_count", ".sgpr_spill_count", ".vgpr_count", ".agpr_count", ".vgpr_spill_count",
           ".private_segment_fixed_size", ".group_segment_fixed_size"]
 
@@ -54,10 +54,11 @@ def kernels(obj):
 
 
 def pretty(mangled):
-    m = re.match(r"_ZN2ks7k_solveILi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E", mangled)
+    m = re.match(r"_ZN2ks7k_solveILi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E", mangled)
     if m:
-        rt, tl, sim, topo, lean = m.groups()
-        return "k_solve<RT=%s,TL=%s,SIM=%s,TOPO=%s,LEAN=%s>" % (rt, tl, sim, topo, lean)
+        rt, tl, sim, topo, lean, mw, slog = m.groups()
+        return "k_solve<RT=%s,TL=%s,SIM=%s,TOPO=%s,LEAN=%s>%s%s" % (rt, tl, sim, topo, lean, " MW" if mw == "1" else "",
+                                                                  " SLOG" if slog == "1" else "")
     try:
         return subprocess.check_output(["c++filt", mangled], text=True).strip()[:90]
     except OSError:
